@@ -18,6 +18,15 @@ all_gather per run (frames_shard.py); each rank uploads its own chunk over
 its own PCIe link in the from-host leg. `--shard independent` gives every
 rank its own sequence instead (no exchange).
 
+A plain run (`--gpus 1 --steps K --warmup W`) sets up, warms up, times the K
+steps of the headline leg and prints the result line. `--full` adds every
+other leg to that line: the from-host legs, the per-stage and roofline
+figures, the hard workload, the per-frame latency, the direct-dispatch re-run,
+the quality check against the ground truth and the CPU baselines.
+`--dump-outputs DIR` writes the pair records the last timed step handed back
+(poses and counts, one DIR/<field>.npy each) so that two builds can be compared
+output for output: the inputs and seeds depend on the arguments alone.
+
 Prints ONE JSON line on rank 0.
 """
 from __future__ import annotations
@@ -748,6 +757,13 @@ def main():
     ap.add_argument("--iters", type=int, default=500, help="RANSAC hypotheses (mIterations)")
     ap.add_argument("--width", type=int, default=640)
     ap.add_argument("--height", type=int, default=480)
+    ap.add_argument("--full", action="store_true",
+                    help="track mode: also run the legs beside the headline (from-host, per-stage and roofline "
+                         "figures, hard workload, per-frame latency, direct-dispatch re-run, ATE, CPU baselines); "
+                         "the --host-steps / --hard-steps / --latency-frames / --no-* options select among them")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="track mode: write the last timed step's pair records (what the timed path hands its "
+                         "caller) as DIR/<field>.npy, float32 for the poses and rmse, float64 for the counts")
     ap.add_argument("--cpu-frames", type=int, default=24, help="oracle sample (frames per timed pass)")
     ap.add_argument("--cpu-reps", type=int, default=5, help="timed oracle passes (median reported)")
     ap.add_argument("--host-steps", type=int, default=1, help="0: skip the from-host legs (they run --steps steps)")
@@ -783,6 +799,8 @@ def main():
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))
     if "WORLD_SIZE" in os.environ and int(os.environ["WORLD_SIZE"]) != args.gpus:
         raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={os.environ['WORLD_SIZE']}")
+    if args.dump_outputs and args.mode != "track":
+        raise SystemExit("--dump-outputs: track mode only")
     if args.mode == "latency":
         latency_mode(args)
         return
@@ -915,8 +933,22 @@ def run_direct_dispatch(args):
             "what": "the headline leg in a child process with HIP's default direct dispatch"}
 
 
+def dump_outputs(dirpath, recs):
+    """The last timed step's pair records (PAIR_DTYPE, one per pair of the
+    batch) as one .npy per field: float fields as float32 (T12 and Tcw as
+    B x 4 x 4), integer counts as float64 (exact)."""
+    os.makedirs(dirpath, exist_ok=True)
+    for name in recs.dtype.names:
+        a = np.ascontiguousarray(recs[name])
+        a = a.astype(np.float32) if a.dtype.kind == "f" else a.astype(np.float64)
+        if a.ndim == 2 and a.shape[1] == 16:
+            a = a.reshape(-1, 4, 4)
+        np.save(os.path.join(dirpath, name + ".npy"), a)
+
+
 def track_mode(args, rank, world, local_rank, dist):
     import torch
+    full = args.full
     from importlib import import_module
     ranks = gather_devices(rank, world, local_rank % max(1, torch.cuda.device_count()), dist)
     pkg = load_pkg()
@@ -962,9 +994,12 @@ def track_mode(args, rank, world, local_rank, dist):
     nb = hb.shape[0]
     d_bgr = torch.from_numpy(hb).to("cuda")                # HBM-resident leg
     d_dep = torch.from_numpy(hd.view(np.int16)).to("cuda")
-    hf = pkg.HostFrames(nb, W, H)                           # from-host legs (pinned)
-    hf.bgr[:] = hb
-    hf.depth[:] = hd
+    host_legs = full and args.host_steps > 0
+    hf = None
+    if host_legs:
+        hf = pkg.HostFrames(nb, W, H)                       # from-host legs (pinned)
+        hf.bgr[:] = hb
+        hf.depth[:] = hd
     cfg = pkg.default_config(W, H, nb, nfeatures=args.nfeatures, iterations=args.iters, seed=pair_seed,
                              detector=(pkg.DETECTOR_ORB_SLAM2 if not adaptive else
                                        pkg.DETECTOR_ADAPTIVE_ORB if inner == "orb" else pkg.DETECTOR_ADAPTIVE_FAST))
@@ -1009,7 +1044,7 @@ def track_mode(args, rank, world, local_rank, dist):
         G = shard.stitch(recs, [0, 1], G_start=np.linalg.inv(gt_poses[0]) if gt_poses is not None else None)
         # ATE over rank 0's first loop (global frames 0 .. L-1 of step 0)
         ate_mm = 1000.0 * tj.ate_rmse(tj.camera_centres(G[0][:L]), gt_poses[:L, :3, 3]) \
-            if rank == 0 and gt_poses is not None else None
+            if full and rank == 0 and gt_poses is not None else None
         res_q = recs[-1][1:]  # a halo step: B genuine pairs, record p+1 = pair (frame p, frame p+1)
         pair_frame0 = 1       # batch frame of record 0 of res_q
 
@@ -1020,13 +1055,16 @@ def track_mode(args, rank, world, local_rank, dist):
         # the headline: inputs resident in HBM
         elapsed, submit, (knn_ms, knn_launches) = leg(False, head_marks)
         # from host memory: every rank uploads its chunk + halo over its own link
-        h_el, h_sub, (h_knn_ms, _) = leg(True) if args.host_steps > 0 else (None, None, (None, 0))
-        sd = None
-        odo.set_timing(True)
-        step(False)
-        odo.synchronize()
-        timings = odo.timings()
-        odo.set_timing(False)
+        k_last = timed_steps[-1]
+        last = ring.all[k_last % rows][:fsm.batch_of(k_last, T, rank, world)[1]].copy()
+        h_el, h_sub, (h_knn_ms, _) = leg(True) if host_legs else (None, None, (None, 0))
+        sd = timings = None
+        if full:
+            odo.set_timing(True)
+            step(False)
+            odo.synchronize()
+            timings = odo.timings()
+            odo.set_timing(False)
         ring.close()
         frames_per_rank = B  # pairs (= new frames) per rank per step
     else:
@@ -1040,7 +1078,7 @@ def track_mode(args, rank, world, local_rank, dist):
         # quality sanity: the untimed first batch's chained poses against the
         # sequence's ground truth (absolute trajectory error, TUM definition)
         ate_mm = None
-        if gt_poses is not None:
+        if full and gt_poses is not None:
             Tcw = tj.chain_poses(res[:L], np.linalg.inv(gt_poses[0]).astype(np.float32))
             ate_mm = 1000.0 * tj.ate_rmse(tj.camera_centres(Tcw), gt_poses[:L, :3, 3])
         # the headline: inputs resident in HBM; every batch's pair records
@@ -1065,7 +1103,7 @@ def track_mode(args, rank, world, local_rank, dist):
         # the last timed batch's records arrived: its match and query counts
         # equal any batch's after the first (every batch cycles the same loop;
         # the RANSAC outcome differs, each pair's seed is its global index)
-        last = ring.all[(K + Wm - 1) % rows][:B]
+        last = ring.all[(K + Wm - 1) % rows][:B].copy()
         # (ADAPTIVE detectors: the per-cell thresholds carry from frame to
         # frame over every batch, so the same loop frames extract differently
         # from batch to batch and only a sanity check applies; their parity
@@ -1078,8 +1116,8 @@ def track_mode(args, rank, world, local_rank, dist):
                 raise SystemExit(f"timed leg: streamed pair records differ from the untimed batch ({f})")
         ring.close()
         h_el = sd = None
-        h_knn_ms = None
-        if args.host_steps > 0:
+        h_knn_ms = timings = None
+        if host_legs:
             # from pinned host memory: one upload per batch on the copy stream
             h_el, h_sub, (h_knn_ms, _) = timed_leg(odo, lambda i: odo.track_batch_host(hf, want_results=False),
                                                    K, Wm, world, dist, coll_dev, ktime)
@@ -1090,12 +1128,13 @@ def track_mode(args, rank, world, local_rank, dist):
                   "ms_per_step": round(sd_el / K * 1e3, 3),
                   "api": "odo_track_batch_host_sparse_depth: BGR uploaded, depth read in place "
                          "(keypoint pixels only) from the pinned host frames"}
-        # per-stage times: one extra (untimed) step with the stage events on
-        odo.set_timing(True)
-        odo.track_batch(d_bgr.data_ptr(), d_dep.data_ptr(), B, want_results=False)
-        odo.synchronize()
-        timings = odo.timings()
-        odo.set_timing(False)
+        if full:
+            # per-stage times: one extra (untimed) step with the stage events on
+            odo.set_timing(True)
+            odo.track_batch(d_bgr.data_ptr(), d_dep.data_ptr(), B, want_results=False)
+            odo.synchronize()
+            timings = odo.timings()
+            odo.set_timing(False)
         frames_per_rank = B
     value = job_throughput(frames_per_rank, K, world, elapsed)
     ms_per_step = elapsed / K * 1e3
@@ -1115,7 +1154,61 @@ def track_mode(args, rank, world, local_rank, dist):
                                 "pinned host buffers (odo_host_alloc), one upload per batch on the copy stream "
                                 "(odo_track_batch_host)"),
                      "sparse_depth": sd}
-    hf.close()
+    if hf is not None:
+        hf.close()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last)
+
+    def result_line():
+        """The headline's result line (rank 0); --full adds its legs to it."""
+        ok = res_q
+        return {
+            "metric": "frames/sec (extract+match+RANSAC-PnP) @640x480, 2000 kp" if not adaptive else
+                      f"frames/sec (ADAPTIVE {'cv::ORB' if inner == 'orb' else 'FAST'} grid + ORB, match, "
+                      f"RANSAC-PnP) @640x480, <=1000 kp",
+            "value": round(value, 2),
+            "unit": "frames/s",
+            "n_gpus": world,
+            "steps": K,
+            "warmup": Wm,
+            "ms_per_step": round(ms_per_step, 3),
+            "step_ms": step_stats(head_marks),
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "u8/i32 (extract, match), f32+f64 (ransac, pnp)",
+            "data": (f"TUM sequence {args.tum} (first {L} frames, cycled)" if args.tum else
+                     "synthetic (ray-cast textured room, closed-loop trajectory; no dataset offline)"),
+            "inputs": "resident in HBM when the timed region starts (from_host: the same path from pinned host memory)",
+            "full": full,
+            "config": {"workload": (f"cfg2 fr1/desk proxy {W}x{H}, {args.nfeatures} kp, RANSAC {args.iters}"
+                                    + (" (hard variant)" if args.workload == "hard" else "")
+                                    if not adaptive else
+                                    f"fr1/desk proxy {W}x{H}, ADAPTIVE 3x3 {'cv::ORB' if inner == 'orb' else 'FAST'} "
+                                    f"grid + ORB (<=1000 kp), "
+                                    f"RANSAC {args.iters}"),
+                       "frames_per_step": B, "global_batch": B * world,
+                       "parallelism": (f"sequence chunks x{world} (+1-frame halo, latch broadcast, pose stitch)"
+                                       if seq_mode else f"frames x{world}"),
+                       "world_size": world,
+                       "backend": dist.get_backend() if world > 1 else None,
+                       "distinct_devices": len({r["pci"] for r in ranks}),
+                       "ranks": ranks,
+                       "mean_knn_queries": round(float(np.mean(res_q["n_queries"])), 1),
+                       "mean_matches": round(float(np.mean(ok["n_matches"])), 1),
+                       "mean_ransac_inliers": round(float(np.mean(ok["n_inliers"])), 1),
+                       "mean_ransac_visited": round(float(np.mean(ok["visited"])), 1)},
+            "host_submit_ms_per_step": round(submit / K * 1e3, 3),
+            "hip_runtime": {"AMD_DIRECT_DISPATCH": os.environ.get("AMD_DIRECT_DISPATCH"),
+                            "dispatch": "worker thread" if os.environ.get("AMD_DIRECT_DISPATCH") == "0" else "direct"},
+        }
+
+    if not full:
+        # a plain run ends here: the headline leg alone
+        odo.close()
+        if rank == 0:
+            print(json.dumps(result_line()), flush=True)
+        return
 
     # keypoints of the frames the statistics' pairs match against (every batch
     # holds the same cycled frames): pair record i's train frame
@@ -1208,56 +1301,19 @@ def track_mode(args, rank, world, local_rank, dist):
                                        f"(extraction and pairs) over every usable core, median of 3 passes"}}
 
     if rank == 0:
-        ok = res_q
-        out = {
-            "metric": "frames/sec (extract+match+RANSAC-PnP) @640x480, 2000 kp" if not adaptive else
-                      f"frames/sec (ADAPTIVE {'cv::ORB' if inner == 'orb' else 'FAST'} grid + ORB, match, "
-                      f"RANSAC-PnP) @640x480, <=1000 kp",
-            "value": round(value, 2),
-            "unit": "frames/s",
-            "n_gpus": world,
-            "steps": K,
-            "warmup": Wm,
-            "ms_per_step": round(ms_per_step, 3),
-            "step_ms": step_stats(head_marks),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "u8/i32 (extract, match), f32+f64 (ransac, pnp)",
-            "data": (f"TUM sequence {args.tum} (first {L} frames, cycled)" if args.tum else
-                     "synthetic (ray-cast textured room, closed-loop trajectory; no dataset offline)"),
-            "inputs": "resident in HBM when the timed region starts (from_host: the same path from pinned host memory)",
-            "config": {"workload": (f"cfg2 fr1/desk proxy {W}x{H}, {args.nfeatures} kp, RANSAC {args.iters}"
-                                    + (" (hard variant)" if args.workload == "hard" else "")
-                                    if not adaptive else
-                                    f"fr1/desk proxy {W}x{H}, ADAPTIVE 3x3 {'cv::ORB' if inner == 'orb' else 'FAST'} "
-                                    f"grid + ORB (<=1000 kp), "
-                                    f"RANSAC {args.iters}"),
-                       "frames_per_step": B, "global_batch": B * world,
-                       "parallelism": (f"sequence chunks x{world} (+1-frame halo, latch broadcast, pose stitch)"
-                                       if seq_mode else f"frames x{world}"),
-                       "world_size": world,
-                       "backend": dist.get_backend() if world > 1 else None,
-                       "distinct_devices": len({r["pci"] for r in ranks}),
-                       "ranks": ranks,
-                       "mean_keypoints": round(nkp_mean, 1),
-                       "mean_knn_queries": round(float(np.mean(res_q["n_queries"])), 1),
-                       "mean_matches": round(float(np.mean(ok["n_matches"])), 1),
-                       "mean_ransac_inliers": round(float(np.mean(ok["n_inliers"])), 1),
-                       "mean_ransac_visited": round(float(np.mean(ok["visited"])), 1),
-                       "ate_mm": round(ate_mm, 3) if ate_mm is not None else None},
+        out = result_line()
+        out["config"]["mean_keypoints"] = round(nkp_mean, 1)
+        out["config"]["ate_mm"] = round(ate_mm, 3) if ate_mm is not None else None
+        out["hip_runtime"]["direct_dispatch_leg"] = direct
+        out.update({
             "stage_ms": {k: round(v, 4) for k, v in timings.items()},
-            "host_submit_ms_per_step": round(submit / K * 1e3, 3),
-            "hip_runtime": {"AMD_DIRECT_DISPATCH": os.environ.get("AMD_DIRECT_DISPATCH"),
-                            "dispatch": "worker thread" if os.environ.get("AMD_DIRECT_DISPATCH") == "0" else "direct",
-                            "direct_dispatch_leg": direct},
             "from_host": from_host,
             "hard_workload": hard,
             "latency": latency,
             "roofline": roofline,
             "roofline_legs": legs,
             "cpu_baseline": cpu,
-        }
+        })
         print(json.dumps(out), flush=True)
 
 

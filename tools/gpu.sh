@@ -9,7 +9,7 @@
 #   tests               pytest -m gpu, the whole suite
 #   tests=F1,F2         pytest -m gpu over the named test files (tests/F1 ...)
 #   smoke               __graft_entry__.smoke()
-#   bench               python bench.py (the driver's default line)      -> bench.json
+#   bench               python bench.py --full (every leg of the line)   -> bench.json
 #   bench=NAME:ARGS     python bench.py ARGS (ARGS with '+' for spaces)  -> NAME.json
 #   benchenv=NAME:ENV:ARGS  the full bench line with VAR=VAL (joined by '/') in the environment
 #   multi               bench.py --gpus 2 --backend gloo: two ranks sharing the GPU
@@ -41,6 +41,7 @@ O=$R/gpurun_out/${1:?outdir}; shift
 mkdir -p "$O"
 P=$R/adaptive-rgbd-localization-mappig_amd
 TUNING=$P/build_tuning/libodo_hip.so
+# the headline leg alone (what a run without --full does; the flags only matter beside --full)
 QUICK="--no-cpu-baseline --no-direct-dispatch-leg --host-steps 0 --hard-steps 0 --latency-frames 0"
 export TMPDIR=/tmp
 
@@ -90,7 +91,7 @@ for step in "$@"; do
       timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1
       tail -1 $O/smoke.log ;;
     bench)
-      timeout -k 10 600 python bench.py > $O/bench.json 2> $O/bench.err
+      timeout -k 10 600 python bench.py --full > $O/bench.json 2> $O/bench.err
       echo "bench ok" ;;
     bench=*)
       spec=${step#bench=}; name=${spec%%:*}; args=$(echo ${spec#*:} | tr '+' ' ')
@@ -102,7 +103,7 @@ for step in "$@"; do
       spec=${step#benchenv=}; name=${spec%%:*}; rest=${spec#*:}
       envs=$(echo ${rest%%:*} | tr '/' ' '); args=$(echo ${rest#*:} | tr '+' ' ')
       [ "$args" = "$rest" ] && args=""
-      env $envs timeout -k 10 600 python bench.py $args > $O/$name.json 2> $O/$name.err
+      env $envs timeout -k 10 600 python bench.py --full $args > $O/$name.json 2> $O/$name.err
       echo "benchenv $name: $(python tools/bsum.py $O/$name.json 2>/dev/null || true)" ;;
     multi)
       timeout -k 10 600 python bench.py --gpus 2 --backend gloo $QUICK > $O/multi_gloo.json 2> $O/multi_gloo.err
@@ -110,7 +111,7 @@ for step in "$@"; do
     kt)
       cd /tmp
       timeout -s KILL 600 rocprofv3 --kernel-trace --stats -d $O/kt -o run --output-format csv -- \
-        python3 $R/bench.py --no-cpu-baseline --no-direct-dispatch-leg --hard-steps 0 --latency-frames 0 > $O/kt_bench.json 2> $O/kt.err
+        python3 $R/bench.py --full --no-cpu-baseline --no-direct-dispatch-leg --hard-steps 0 --latency-frames 0 > $O/kt_bench.json 2> $O/kt.err
       cd $R
       T=$(find $O/kt -name '*kernel_trace.csv' -print -quit)
       python tools/rocprof_timed_region.py "$T" $O/kt_bench.json $O/rocprof_timed_region.json > $O/rtr.log 2>&1 || true
@@ -121,7 +122,7 @@ for step in "$@"; do
       name=${step#ktn=}
       cd /tmp
       timeout -s KILL 600 rocprofv3 --kernel-trace -d $O/$name -o run --output-format csv -- \
-        python3 $R/bench.py --no-cpu-baseline --no-direct-dispatch-leg --latency-frames 0 --host-steps 0 $AB_ARGS > $O/$name.json 2> $O/$name.err
+        python3 $R/bench.py --full --no-cpu-baseline --no-direct-dispatch-leg --latency-frames 0 --host-steps 0 $AB_ARGS > $O/$name.json 2> $O/$name.err
       cd $R
       echo "ktn $name: $(python tools/bsum.py $O/$name.json 2>/dev/null || true)" ;;
     ktv=*)
@@ -129,7 +130,7 @@ for step in "$@"; do
       v=${step#ktv=}
       cd /tmp
       ODO_LIB=$(lib_of $v) timeout -s KILL 600 rocprofv3 --kernel-trace -d $O/ktv_$v -o run --output-format csv -- \
-        python3 $R/bench.py --no-cpu-baseline --no-direct-dispatch-leg --latency-frames 0 --host-steps 0 --hard-steps 0 $AB_ARGS \
+        python3 $R/bench.py --full --no-cpu-baseline --no-direct-dispatch-leg --latency-frames 0 --host-steps 0 --hard-steps 0 $AB_ARGS \
         > $O/ktv_$v.json 2> $O/ktv_$v.err
       cd $R
       echo "ktv $v: $(python tools/bsum.py $O/ktv_$v.json 2>/dev/null || true)" ;;
@@ -202,14 +203,14 @@ for step in "$@"; do
       spec=${step#envbench=}; name=${spec%%:*}; rest=${spec#*:}
       envs=$(echo ${rest%%:*} | tr '/' ' '); args=$(echo ${rest#*:} | tr '+' ' ')
       [ "$args" = "$rest" ] && args=""
-      env $envs ODO_LIB=$TUNING timeout -k 10 300 python bench.py --no-cpu-baseline --no-direct-dispatch-leg --latency-frames 0 --host-steps 0 \
+      env $envs ODO_LIB=$TUNING timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-direct-dispatch-leg --latency-frames 0 --host-steps 0 \
         $args > $O/$name.json 2> $O/$name.err
       echo "envbench $name: $(python tools/bsum.py $O/$name.json 2>/dev/null || true)" ;;
     ab=*)
       spec=${step#ab=}; n=${spec%%:*}; vs=$(echo ${spec#*:} | tr ',' ' ')
       for i in $(seq 1 $n); do
         for v in $vs; do
-          ODO_LIB=$(lib_of $v) timeout -k 10 300 python bench.py --no-cpu-baseline --no-direct-dispatch-leg --latency-frames 0 --host-steps 0 \
+          ODO_LIB=$(lib_of $v) timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-direct-dispatch-leg --latency-frames 0 --host-steps 0 \
             $AB_ARGS > $O/ab_${v}_$i.json 2> $O/ab_${v}_$i.err
           echo "ab $v $i: $(python tools/bsum.py $O/ab_${v}_$i.json 2>/dev/null || true)"
         done

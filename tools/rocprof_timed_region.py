@@ -5,7 +5,8 @@ from a rocprof summary of the timed region).
 bench.py (track mode, one GPU) launches one k_gray (or, with the one-launch
 pyramid, one k_pyramid) per batch: 2 untimed
 statistics batches, W warm-up steps, then the K timed steps of the
-HBM-resident leg; then W + K steps of each from-host leg. The timed region of
+HBM-resident leg; with --full, then W + K steps of each from-host leg (the
+bench line's roofline, read below, is a --full figure too). The timed region of
 a leg is every kernel that starts between the leg's first timed k_gray and the
 next leg's first k_gray (the legs are separated by a device synchronize).
 

@@ -1700,19 +1700,10 @@ __global__ void __launch_bounds__(64 * LN_WAVES, 2) k_ransac_lanes(RansacBufs B,
 }
 
 // ---------------------------------------------------------------- final
-// mode 0: every pair. mode 1: after the first eval launch — record which pairs
-// are finished (phase[p] = 1) and finalize those. mode 2: finalize the others.
-__global__ void __launch_bounds__(64) k_ransac_final(RansacBufs B, RansacCfg cfg, int mode, int* phase) {
+__global__ void __launch_bounds__(64) k_ransac_final(RansacBufs B, RansacCfg cfg) {
     __builtin_amdgcn_s_setprio(ODO_WAVE_PRIO);  // latency-bound: issue ahead of co-resident extraction waves
     const int p = blockIdx.x;
     const int lane = threadIdx.x;
-    if (mode == 1) {
-        const int dn = B.st[p].done;
-        if (lane == 0) phase[p] = dn ? 1 : 0;
-        if (!dn) return;
-    } else if (mode == 2 && phase[p] == 1) {
-        return;
-    }
 
     __shared__ Rng s_rng;
     __shared__ double s_d2[64];
@@ -1726,7 +1717,7 @@ __global__ void __launch_bounds__(64) k_ransac_final(RansacBufs B, RansacCfg cfg
     // finisher's lock attempt raced a holder's release and re-check (the
     // ready store and the lock CAS are not ordered with each other without a
     // full fence, which measured 4 % of the batch step) - is completed here
-    if (active && mode != 1 && !B.no_fold && !ld_relaxed(&S->done)) try_fold_wave(B, cfg, p, lane);
+    if (active && !B.no_fold && !ld_relaxed(&S->done)) try_fold_wave(B, cfg, p, lane);
     const int ng = S->ng, words = S->words;
     const unsigned minInl = (unsigned)cfg.min_inlier_th;
     uint32_t* BM = B.best_mask + (size_t)p * B.mask_words;
@@ -2164,14 +2155,13 @@ static void ransac_eval_lds_attr() {
     }
 }
 
-void launch_ransac(hipStream_t st, const void* good, const int* n_good, const int* n_matches,
-                   const odo_dmatch* matches, const float* xyz, int kp_cap, int slot0, int match_cap, RansacCfg cfg,
-                   const double* latch, const int* pair_valid, int min_matches, odo_rng* rng_io, void* scratch,
-                   uint32_t* best_mask, int mask_words, odo_pair_result* res, float* T12, int npairs, int part,
-                   int* phase, int* open_hint) {
-    ransac_eval_lds_attr();
-    cfg.h0 = EV_H0;
-    cfg.fold_wave = 0;
+// the launch's view of the pair buffers and the scratch: every hypothesis of
+// every pair, folded
+static RansacBufs ransac_bufs(const void* good, const int* n_good, const int* n_matches, const odo_dmatch* matches,
+                              const float* xyz, int kp_cap, int slot0, int match_cap, const RansacCfg& cfg,
+                              const double* latch, const int* pair_valid, int min_matches, odo_rng* rng_io,
+                              void* scratch, uint32_t* best_mask, int mask_words, odo_pair_result* res, float* T12,
+                              int npairs) {
     RansacBufs B = carve(scratch, npairs, match_cap, mask_words, cfg);
     B.good = (const SortElR*)good;
     B.n_good = n_good;
@@ -2187,30 +2177,48 @@ void launch_ransac(hipStream_t st, const void* good, const int* n_good, const in
     B.best_mask = best_mask;
     B.res = res;
     B.T12 = T12;
-    const int H = std::max(cfg.iterations, 0);
     B.h_lo = 0;
-    B.h_hi = H;
+    B.h_hi = std::max(cfg.iterations, 0);
     B.no_fold = 0;
-    if (part == 3) {
-        // hypotheses mode, one pair: samples of all H, evaluation of [h0, h1)
-        // only (h0/h1 passed in phase[0..1]), no fold and no outputs
-        B.h_lo = std::max(0, phase[0]);
-        B.h_hi = std::min(H, phase[1]);
-        B.no_fold = 1;
-        hipLaunchKernelGGL(k_ransac_prep, dim3(npairs), dim3(256), 0, st, B, cfg);
-        if (B.h_hi > B.h_lo) {
-            const int ya = B.h_lo / EV_WAVES, yb = (B.h_hi + EV_WAVES - 1) / EV_WAVES;
-            hipLaunchKernelGGL(k_ransac_eval, dim3(npairs, yb - ya), dim3(64 * EV_WAVES), EV_LDS, st,
-                               B, cfg, 0, ya, yb * EV_WAVES);
-        }
-        return;
+    return B;
+}
+
+// hypotheses mode: samples of all H, evaluation of [h_lo, h_hi) only, no fold
+// and no outputs
+void launch_ransac_hyps(hipStream_t st, const void* good, const int* n_good, const int* n_matches,
+                        const odo_dmatch* matches, const float* xyz, int kp_cap, int slot0, int match_cap,
+                        RansacCfg cfg, const double* latch, const int* pair_valid, int min_matches, odo_rng* rng_io,
+                        void* scratch, uint32_t* best_mask, int mask_words, odo_pair_result* res, float* T12,
+                        int npairs, int h_lo, int h_hi) {
+    ransac_eval_lds_attr();
+    cfg.h0 = EV_H0;
+    cfg.fold_wave = 0;
+    RansacBufs B = ransac_bufs(good, n_good, n_matches, matches, xyz, kp_cap, slot0, match_cap, cfg, latch, pair_valid,
+                               min_matches, rng_io, scratch, best_mask, mask_words, res, T12, npairs);
+    B.h_lo = std::max(0, h_lo);
+    B.h_hi = std::min(B.h_hi, h_hi);
+    B.no_fold = 1;
+    hipLaunchKernelGGL(k_ransac_prep, dim3(npairs), dim3(256), 0, st, B, cfg);
+    if (B.h_hi > B.h_lo) {
+        const int ya = B.h_lo / EV_WAVES, yb = (B.h_hi + EV_WAVES - 1) / EV_WAVES;
+        hipLaunchKernelGGL(k_ransac_eval, dim3(npairs, yb - ya), dim3(64 * EV_WAVES), EV_LDS, st, B, cfg, 0, ya,
+                           yb * EV_WAVES);
     }
+}
+
+void launch_ransac(hipStream_t st, const void* good, const int* n_good, const int* n_matches,
+                   const odo_dmatch* matches, const float* xyz, int kp_cap, int slot0, int match_cap, RansacCfg cfg,
+                   const double* latch, const int* pair_valid, int min_matches, odo_rng* rng_io, void* scratch,
+                   uint32_t* best_mask, int mask_words, odo_pair_result* res, float* T12, int npairs,
+                   int* open_hint) {
+    ransac_eval_lds_attr();
+    const RansacBufs B = ransac_bufs(good, n_good, n_matches, matches, xyz, kp_cap, slot0, match_cap, cfg, latch,
+                                     pair_valid, min_matches, rng_io, scratch, best_mask, mask_words, res, T12, npairs);
+    const int H = B.h_hi;
     // Two eval launches: the first h0 hypotheses of every pair (the >80% break
     // usually ends a pair within them), then the rest, which only pairs still
     // folding take up — so the speculative hypotheses of finished pairs do
-    // not compete with the long ones. part 1 = prep, first launch and the
-    // finished pairs' outputs (phase[] marks them); part 2 = the rest; part 0
-    // = both.
+    // not compete with the long ones.
     // hypotheses of the first launch: odo_kernel_forms.ransac_first_hyps, else
     // ODO_EV_H0 (tuning), else EV_H0
     static const int h0env = [] {
@@ -2221,67 +2229,62 @@ void launch_ransac(hipStream_t st, const void* good, const int* n_good, const in
     // a lone pair (the per-stage odo_ransac, a one-frame batch) starts every
     // hypothesis at once: the device is otherwise idle, and the visited
     // hypotheses beyond the first row no longer wait for the first launch
-    // (the fold and the aborts make the result independent of the schedule)
+    // (the fold and the aborts make the result independent of the launch order)
     const int h0 = npairs == 1 ? H : std::min(H, h0k);
     cfg.h0 = h0;
     cfg.fold_wave = npairs == 1;
-    if (part != 2) {
-        hipLaunchKernelGGL(k_ransac_prep, dim3(npairs), dim3(256), 0, st, B, cfg);
-        if (h0 > 0) {
-            // rows of EV_WAVES hypotheses; a first launch of fewer runs that many waves
-            const int r0 = (h0 + EV_WAVES - 1) / EV_WAVES, nw = std::min(h0, EV_WAVES);
-            hipLaunchKernelGGL(k_ransac_eval, dim3(npairs, r0), dim3(64 * nw), EV_LDS, st, B, cfg, 0, 0, h0);
-        }
-        if (part == 1) hipLaunchKernelGGL(k_ransac_final, dim3(npairs), dim3(64), 0, st, B, cfg, 1, phase);
+    hipLaunchKernelGGL(k_ransac_prep, dim3(npairs), dim3(256), 0, st, B, cfg);
+    if (h0 > 0) {
+        // rows of EV_WAVES hypotheses; a first launch of fewer runs that many waves
+        const int r0 = (h0 + EV_WAVES - 1) / EV_WAVES, nw = std::min(h0, EV_WAVES);
+        hipLaunchKernelGGL(k_ransac_eval, dim3(npairs, r0), dim3(64 * nw), EV_LDS, st, B, cfg, 0, 0, h0);
     }
-    if (part != 1) {
-        // the second launch's waves stride over the remaining hypotheses
-        // [h0, H): ev2_rows() rows of EV_WAVES per pair in flight (ODO_EV2_ROWS)
-        const int rows = (H - h0 + EV_WAVES - 1) / EV_WAVES;
-        if (rows > 0) {
-            if (ev2_list()) {
-                hipLaunchKernelGGL(k_ransac_open, dim3(1), dim3(256), 0, st, B, npairs);
-                // which of the two kernels takes the open pairs: decided on the
-                // host from the previous batch's open count on this frame set
-                // (open_hint, page-locked, copied back asynchronously), so
-                // only one of them is launched; both give the same results
-                // (no hint yet, -1: the first batch of a set: both are
-                // launched and the open count on the device picks one)
-                const int lanes = ln_groups();
-                const int tmin = cfg.lanes_min_open > 0 ? cfg.lanes_min_open : ln_min_open();
-                const int hint = open_hint ? *reinterpret_cast<volatile int*>(open_hint) : 0;
-                const bool use_lanes = lanes && open_hint && hint >= tmin;
-                // the pairs still open after the first launch are the long
-                // ones (the bench's sequence: 2 of 64, visiting 36 and 380
-                // hypotheses): the work list folds them with the whole wave
-                // (64 ready flags per load, try_fold_wave) instead of lane
-                // 0's serial coherent loads, ~0.4 us per visited hypothesis
-                RansacCfg cfg2 = cfg;
-                cfg2.fold_wave = EV2_FOLD_WAVE;
-                if (lanes && hint < 0) {
-                    hipLaunchKernelGGL(k_ransac_eval_list, dim3(ev2_list()), dim3(64 * EV_WAVES), EV_LDS, st, B, cfg2,
-                                       h0, rows, tmin - 1);
-                    hipLaunchKernelGGL(k_ransac_lanes, dim3(lanes), dim3(64 * LN_WAVES), 0, st, B, cfg, B.lslab,
-                                       lanes * LN_WAVES, tmin);
-                } else if (use_lanes)
-                    hipLaunchKernelGGL(k_ransac_lanes, dim3(lanes), dim3(64 * LN_WAVES), 0, st, B, cfg, B.lslab,
-                                       lanes * LN_WAVES, 1);
-                else
-                    hipLaunchKernelGGL(k_ransac_eval_list, dim3(ev2_list()), dim3(64 * EV_WAVES), EV_LDS, st, B, cfg2,
-                                       h0, rows, 1 << 30);
-                if (open_hint) (void)hipMemcpyAsync(open_hint, B.open_cnt, sizeof(int), hipMemcpyDeviceToHost, st);
-            } else {
-                hipLaunchKernelGGL(k_ransac_eval, dim3(npairs, std::min(rows, ev2_rows())), dim3(64 * EV_WAVES),
-                                   EV_LDS, st, B, cfg, h0, 0, H);
-            }
+    // the second launch's waves stride over the remaining hypotheses
+    // [h0, H): ev2_rows() rows of EV_WAVES per pair in flight (ODO_EV2_ROWS)
+    const int rows = (H - h0 + EV_WAVES - 1) / EV_WAVES;
+    if (rows > 0) {
+        if (ev2_list()) {
+            hipLaunchKernelGGL(k_ransac_open, dim3(1), dim3(256), 0, st, B, npairs);
+            // which of the two kernels takes the open pairs: decided on the
+            // host from the previous batch's open count on this frame set
+            // (open_hint, page-locked, copied back asynchronously), so
+            // only one of them is launched; both give the same results
+            // (no hint yet, -1: the first batch of a set: both are
+            // launched and the open count on the device picks one)
+            const int lanes = ln_groups();
+            const int tmin = cfg.lanes_min_open > 0 ? cfg.lanes_min_open : ln_min_open();
+            const int hint = open_hint ? *reinterpret_cast<volatile int*>(open_hint) : 0;
+            const bool use_lanes = lanes && open_hint && hint >= tmin;
+            // the pairs still open after the first launch are the long
+            // ones (the bench's sequence: 2 of 64, visiting 36 and 380
+            // hypotheses): the work list folds them with the whole wave
+            // (64 ready flags per load, try_fold_wave) instead of lane
+            // 0's serial coherent loads, ~0.4 us per visited hypothesis
+            RansacCfg cfg2 = cfg;
+            cfg2.fold_wave = EV2_FOLD_WAVE;
+            if (lanes && hint < 0) {
+                hipLaunchKernelGGL(k_ransac_eval_list, dim3(ev2_list()), dim3(64 * EV_WAVES), EV_LDS, st, B, cfg2,
+                                   h0, rows, tmin - 1);
+                hipLaunchKernelGGL(k_ransac_lanes, dim3(lanes), dim3(64 * LN_WAVES), 0, st, B, cfg, B.lslab,
+                                   lanes * LN_WAVES, tmin);
+            } else if (use_lanes)
+                hipLaunchKernelGGL(k_ransac_lanes, dim3(lanes), dim3(64 * LN_WAVES), 0, st, B, cfg, B.lslab,
+                                   lanes * LN_WAVES, 1);
+            else
+                hipLaunchKernelGGL(k_ransac_eval_list, dim3(ev2_list()), dim3(64 * EV_WAVES), EV_LDS, st, B, cfg2,
+                                   h0, rows, 1 << 30);
+            if (open_hint) (void)hipMemcpyAsync(open_hint, B.open_cnt, sizeof(int), hipMemcpyDeviceToHost, st);
+        } else {
+            hipLaunchKernelGGL(k_ransac_eval, dim3(npairs, std::min(rows, ev2_rows())), dim3(64 * EV_WAVES),
+                               EV_LDS, st, B, cfg, h0, 0, H);
         }
-        hipLaunchKernelGGL(k_ransac_final, dim3(npairs), dim3(64), 0, st, B, cfg, part == 2 ? 2 : 0, phase);
     }
+    hipLaunchKernelGGL(k_ransac_final, dim3(npairs), dim3(64), 0, st, B, cfg);
 }
 
-// Hypotheses mode readback / finish over the scratch of a part-3 launch
+// Hypotheses mode readback / finish over the scratch of a launch_ransac_hyps
 // (one pair): per-hypothesis (err, cnt, T) of [h0, h1), then the outputs of
-// the folded run (k_ransac_final mode 0: T12 / inlier mask of best_h when this
+// the folded run (k_ransac_final: T12 / inlier mask of best_h when this
 // process evaluated it, identity fallback when nothing was valid, and the
 // caller's rand() state after exactly the visited draws).
 void ransac_read_hyps(hipStream_t st, void* scratch, int match_cap, int mask_words, RansacCfg cfg, int h0, int h1,
@@ -2308,7 +2311,7 @@ void launch_ransac_finish(hipStream_t st, void* scratch, int match_cap, int mask
     B.res = res;
     B.T12 = T12;
     hipLaunchKernelGGL(k_ransac_install, dim3(1), dim3(1), 0, st, B, best_h, visited, valid, best_cnt, rmse);
-    hipLaunchKernelGGL(k_ransac_final, dim3(1), dim3(64), 0, st, B, cfg, 0, (int*)nullptr);
+    hipLaunchKernelGGL(k_ransac_final, dim3(1), dim3(64), 0, st, B, cfg);
 }
 
 // hypotheses mode on the device: this rank's summaries [h0, h1) into d_block
@@ -2336,7 +2339,7 @@ void launch_hyp_finish(hipStream_t st, void* scratch, int match_cap, int mask_wo
     B.res = res;
     B.T12 = T12;
     hipLaunchKernelGGL(k_hyp_install_dev, dim3(1), dim3(1), 0, st, B, d_fold);
-    hipLaunchKernelGGL(k_ransac_final, dim3(1), dim3(64), 0, st, B, cfg, 0, (int*)nullptr);
+    hipLaunchKernelGGL(k_ransac_final, dim3(1), dim3(64), 0, st, B, cfg);
     hipLaunchKernelGGL(k_hyp_payload, dim3(1), dim3(256), 0, st, B, d_fold, h0, h1, rank0, good, ng, payload, words);
 }
 int hyp_payload_words(int ng) { return HYP_PAYLOAD_HDR + 4 * std::max(ng, 0); }

@@ -5,13 +5,22 @@
 // cross-frame state the reference keeps in globals: the previous frame
 // (Tracking::mpLastFrame) and the DepthCovariance latch.
 //
-// Batches are pipelined over two streams. The extraction stream rolls the
-// previous batch's last frame into slot 0 of a frame set and extracts the new
-// frames into slots 1..n; the pair stream then matches, runs RANSAC and PnP on
-// that set. Frame sets (and the RANSAC scratch) alternate between batches, so
-// batch k+1's throughput-bound extraction overlaps batch k's latency-bound
-// pair stages; per-set events order the reuse (set s is rewritten only after
-// the pair stages of batch k-1 that read it have finished).
+// Batches are pipelined over an extraction stream, two pair streams and NSETS
+// frame sets (each with its pair buffers and RANSAC scratch). Batch b uses set
+// b % NSETS and pair stream b % 2:
+//   extraction stream: pyramid, FAST, octree, blur, descriptors of the new
+//     frames into slots 1..n of the set;
+//   pair stream: RANSAC's rand() words (seed-only, ahead of the extraction's
+//     end), then the roll (the previous batch's last frame into slot 0), the
+//     keypoint geometry, kNN-2, matching, the DepthCovariance latch, RANSAC
+//     and PnP.
+// So batch b+1's throughput-bound extraction overlaps batch b's latency-bound
+// pair stages, and one batch's long RANSAC / PnP overlaps the next batch's
+// pair stages on the other pair stream. One event per set ("PnP of this set
+// done") orders the reuse: a set is rewritten only after the PnP of the batch
+// that last used it, and the extraction of batch b waits for the PnP of batch
+// b - PYR_WAIT. (The ADAPTIVE detectors, stage timing and host-input batches
+// keep the roll and the geometry on the extraction stream.)
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -118,24 +127,24 @@ struct DevArena {
 // Frame sets in flight (4): batch k extracts into set k%NSETS while the pair and
 // PnP stages of batches k-1 and k-2 still read theirs, so the extraction
 // stream never waits on the PnP latency of the batch just before it.
-#ifndef ODO_EVFENCE
-#define ODO_EVFENCE 1  // stream-ordering events: 0 default (system-scope fence), 1 no system fence, 2 device-scope release
-#endif
-#define ODO_SYNC_EVENT_FLAGS \
-    (hipEventDisableTiming | (ODO_EVFENCE == 1 ? hipEventDisableSystemFence : ODO_EVFENCE == 2 ? hipEventReleaseToDevice : 0u))
-#ifndef KNN_GATE
-#define KNN_GATE 0
-#endif
-#ifndef PYR_WAIT
-#define PYR_WAIT 3  // measured: 1.921-1.938 vs 1.933-1.989 ms per step, hard workload unchanged (profiles/r05_q)
-#endif
-#ifndef ODO_NSETS
-#define ODO_NSETS 4  // measured: 4 sets 60.1k vs 3 sets 57.7k frames/s (256-frame batches)
-#endif
-constexpr int NSETS = ODO_NSETS;
-// batch b - PYR_WAIT must not share batch b's frame set: its PnP events are
-// re-recorded by batch b - PYR_WAIT + NSETS
-static_assert(PYR_WAIT >= 0 && PYR_WAIT < ODO_NSETS, "PYR_WAIT must be below ODO_NSETS");
+// measured: 4 sets 60.1k vs 3 sets 57.7k frames/s (256-frame batches).
+// The extraction of batch b waits for the PnP of batch b - PYR_WAIT, so the
+// pyramid does not share the CUs with a PnP / RANSAC evaluation still running
+// from an earlier batch (measured: 3, 1.921-1.938 vs 1.933-1.989 ms per step,
+// hard workload unchanged, profiles/r05_q).
+constexpr int NSETS = 4, PYR_WAIT = 3;
+// The next batch's roll reads this set's last frame on its pair stream, before
+// its PnP: the batch that reuses this set waits for that PnP through PYR_WAIT,
+// which therefore has to be at least 1. And batch b - PYR_WAIT must not share
+// batch b's frame set: its PnP-done event is re-recorded by batch
+// b - PYR_WAIT + NSETS.
+static_assert(PYR_WAIT >= 1 && PYR_WAIT < NSETS, "PYR_WAIT must lie in [1, NSETS - 1]");
+// The context's events only order its streams against each other (and tell
+// the host that inputs were consumed): none needs the system-scope cache
+// writeback + invalidate a default event record performs, which on this part
+// also disturbs every kernel then running (round 5: ~10 records per batch;
+// DESIGN §4 Pipelining)
+constexpr unsigned SYNC_EVENT_FLAGS = hipEventDisableTiming | hipEventDisableSystemFence;
 // output rows per resize workgroup
 constexpr int RZ_RB = 16;
 
@@ -147,39 +156,18 @@ struct odo_ctx {
     HypSession* hs = nullptr;
     int device = 0;
     hipStream_t stream = nullptr;   // extraction
-    hipStream_t pstream = nullptr;  // pair stages
-    hipStream_t pstream2 = nullptr;  // pair stages of odd batches (schedule 5)
-    hipStream_t pstream3 = nullptr;  // third pair stream (schedule 5, ODO_PSTREAMS=3)
-    int npstreams = 2;
-    bool knn_pair = true;  // schedule 5 (ODO_KNN_PAIR=0: on the extraction stream): kNN-2 at the head of the pair stream, 88.2k vs 86.5k frames/s (kNN roofline 0.85 vs 0.90)
-    hipStream_t cur_p = nullptr;     // pair stream of the batch being queued
-    // KNN_GATE / ODO_KNN_GATE (tuning): the next batch's extraction waits
-    // for this batch's kNN-2 (no pyramid / kNN-2 overlap)
-    bool knn_gate = KNN_GATE != 0;
-    // the extraction of batch b waits for the PnP of batch b - pyr_wait (0:
-    // not), so the pyramid does not share the CUs with a PnP / RANSAC
-    // evaluation still running from an earlier batch (PYR_WAIT; ODO_PYR_WAIT)
-    int pyr_wait = PYR_WAIT;
-    int batch_set[8] = {};  // set of batch b at [b & 7]
-    hipEvent_t ev_knn = nullptr;
-    bool knn_rec = false;
+    // pair stages of even / odd batches (kNN-2 at the head of the pair stream
+    // instead of on the extraction stream: 88.2k vs 86.5k frames/s)
+    hipStream_t pstream = nullptr, pstream2 = nullptr;
     std::vector<hipStream_t> owned;  // streams created (the rest alias them)
-    hipEvent_t ev_latch = nullptr;   // after the last queued k_latch (schedule 5)
+    hipEvent_t ev_latch = nullptr;   // after the last queued k_latch
     bool latch_rec = false;
-    bool latched = false;  // this batch leaves the latch kernel out (see run_pairs)
-    // ODO_GEO_PAIR: this batch's geometry and roll are on its pair stream;
-    // ev_geo[set] follows the set's geometry kernel (the next batch's roll
-    // reads the last frame's kun / xyz / uR); host_call: a track_host
-    // batch (its depth reads must stay on the extraction stream)
-    bool geo_pair = false, host_call = false;
-    // ODO_EARLY_WAIT (run_extract): the next batch's extraction-stream waits
-    // were queued during this one (pre_waited = that batch's counter)
-    bool early_waits = false;
-    bool defer_pdone = false;  // odo_track_batch_async: PnP-done events after the result copy
-    uint64_t pre_waited = ~(uint64_t)0;
+    // ev_geo[set] follows the set's geometry kernel when it ran on the batch's
+    // pair stream (geo_rec; the next batch's roll reads the last frame's
+    // kun / xyz / uR)
     hipEvent_t ev_geo[NSETS] = {};
     bool geo_rec[NSETS] = {};
-    uint64_t batch_counter = 0;
+    uint64_t batch_counter = 0;  // batch b uses frame set b % NSETS and pair stream b % 2
     int W = 0, H = 0, maxb = 0, slots = 0, nlevels = 0;
     std::vector<LevelDesc> lv_h;
     std::vector<CellDesc> cells_h;
@@ -205,7 +193,7 @@ struct odo_ctx {
     size_t pyr_size = 0, keys_per_frame = 0;
     FrameCalib cal{};
     RansacCfg rcfg{};
-    // frame buffers ([2 sets][slots])
+    // frame buffers ([NSETS][slots])
     uint8_t *pyr = nullptr, *blur = nullptr;
     uint32_t* cand = nullptr;
     int* cand_cnt = nullptr;
@@ -275,7 +263,6 @@ struct odo_ctx {
         float* T12 = nullptr;
         void* edges = nullptr;
         uint8_t* pnp_mask = nullptr;
-        int* pair_phase = nullptr;  // per pair: finished by RANSAC part 1
     } pb[NSETS];
     // sequence state: the last tracked batch sits in frame set seq_set (its
     // last frame at slot seq_n); getters read view_set / view_n
@@ -286,38 +273,19 @@ struct odo_ctx {
     std::vector<int> valid_h;
     hipEvent_t ev[16];
     int nev = 0;
-    hipStream_t side = nullptr;  // RANSAC rand() words, ahead of the pair stages
-    hipStream_t pnpa = nullptr;  // PnP of the pairs RANSAC part 1 finished
-    hipStream_t pnpb = nullptr;  // PnP of the pairs RANSAC part 2 finished
-    hipEvent_t ev_xdone[NSETS] = {}, ev_raw[NSETS] = {};
-    // schedule 5 with ODO_BLUR_STREAM=1: the pyramid blur of a batch runs on
-    // its own stream beside FAST + octree, joined before finalize (measured
-    // 76.2 k vs 77.7 k frames/s without: the CUs are already shared with the
-    // pair streams, so it stays off by default)
-    hipStream_t bstream = nullptr;
-    hipEvent_t ev_pyr[NSETS] = {}, ev_blur[NSETS] = {};
-    // per set: RANSAC part 1 / part 2 done, PnP A / PnP B done
-    hipEvent_t ev_ra[NSETS] = {}, ev_rb[NSETS] = {}, ev_pa[NSETS] = {}, ev_pb[NSETS] = {};
+    // per set: the extraction of the set's batch is done; the PnP of the
+    // set's batch (and, async, its result copy) is done
+    hipEvent_t ev_xdone[NSETS] = {}, ev_pnp_done[NSETS] = {};
     bool pdone_rec[NSETS] = {};
-    hipStream_t pdone_st[NSETS] = {};  // the stream that last recorded ev_pa / ev_pb of a set
+    hipStream_t pdone_st[NSETS] = {};  // the stream that last recorded ev_pnp_done of a set
+    // ODO_SERIAL_STREAMS (tuning): every stream aliases the extraction stream.
+    // (Four streams in all, the copy stream included: every stream beyond the
+    // process's GPU_MAX_HW_QUEUES (4) hardware queues would share one with
+    // another stream and serialise behind it.)
     bool serial = false;
     bool timing = false;
-    // stream layout (ODO_SCHED). Only the streams a schedule uses are created:
-    // every stream beyond the process's GPU_MAX_HW_QUEUES (4) hardware queues
-    // shares one with another stream and serialises behind it.
-    // 5 (default) = extraction (+ kNN-2) | two pair streams taking alternate
-    //     batches, each running its batch's rand() words, match, RANSAC and
-    //     PnP, so one batch's long RANSAC/PnP overlaps the next batch's pair
-    //     stages (the DepthCovariance latch kernels are ordered by an event):
-    //     52.9k frames/s at 128-frame batches;
-    // 2 = extraction | side (words) | pair stages | one PnP stream: 42.1k;
-    // 1 = as 2 with two PnP launches on two streams: 41.9k;
-    // 0 = words on the extraction stream; 3 = kNN-2 + words on the side
-    //     stream; 4 = words at the head of the pair stream.
-    int sched = 5;
     // ODO_SKIP (measurement only; results are invalid when set): bit 0 skips
-    // the PnP launches, bit 1 RANSAC part 2, bit 2 every pair stage, bit 3 kNN-2,
-    // bit 4 RANSAC (schedule 2)
+    // the PnP launch, bit 2 every pair stage, bit 3 kNN-2, bit 4 RANSAC
     int skip = 0;
     // ADAPTIVE grid extractor (ODO_DETECTOR_ADAPTIVE_FAST): cell / band
     // tables and per-batch scratch (extraction stream only), plus the
@@ -376,45 +344,39 @@ static inline size_t fbase(const odo_ctx* c, int set) { return (size_t)set * c->
 // the set the next batch extracts into
 static inline int next_set(const odo_ctx* c) { return (c->seq_set + 1) % NSETS; }
 
-#ifndef ODO_WAIT_DEDUP
-#define ODO_WAIT_DEDUP 1
-#endif
-#ifndef ODO_EARLY_WAIT
-#define ODO_EARLY_WAIT 0
-#endif
-#ifndef ODO_GEO_PAIR
-// schedule 5, device inputs: the keypoint geometry (undistort, depth) and the
-// slot-0 roll run at the head of the batch's pair stream instead of at the
-// end of the extraction stream, the step's critical path (round 6: 152.0-152.6
-// vs 150.9-151.3 k frames/s, three alternations on one box, profiles/r06_d)
-#define ODO_GEO_PAIR 1
-#endif
-// `st` waits until the PnP launches (and, async, the result copy) of the batch
-// that last used frame set `set` are done. Every wait is a barrier packet the
-// queue processes in order: schedule 5 records ev_pa and ev_pb at the same
-// point of one stream, so one of them is enough, and none is needed on that
-// stream itself (ODO_WAIT_DEDUP; 0 = the round-5 waits on both events).
+// The per-frame output arrays of frame slot `slot` (fbase(set) + slot in set)
+struct FrameSlot {
+    orb_kp* kps;
+    uint8_t* desc;
+    float *kun, *xyz, *ur;
+    int* nkp;
+};
+static inline FrameSlot frame_at(const odo_ctx* c, size_t slot) {
+    const size_t KC = (size_t)c->kp_cap;
+    return {c->kps + slot * KC,     c->desc + slot * KC * 32, c->kun + slot * KC * 2,
+            c->xyz + slot * KC * 3, c->ur + slot * KC,        c->nkp + slot};
+}
+
+// `st` waits until the PnP launch (and, async, the result copy) of the batch
+// that last used frame set `set` is done. Every wait is a barrier packet the
+// queue processes in order, so each is worth leaving out: one event per set is
+// recorded after the batch's last pair-stream work, and the stream that
+// recorded it needs no wait at all (it is ordered behind that work already).
 static int wait_pnp_done(odo_ctx* c, hipStream_t st, int set) {
-    if (ODO_WAIT_DEDUP && c->sched == 5) {
-        if (st != c->pdone_st[set]) HIPCHK(hipStreamWaitEvent(st, c->ev_pb[set], 0));
-        return ODO_OK;
-    }
-    HIPCHK(hipStreamWaitEvent(st, c->ev_pa[set], 0));
-    HIPCHK(hipStreamWaitEvent(st, c->ev_pb[set], 0));
+    if (st != c->pdone_st[set]) HIPCHK(hipStreamWaitEvent(st, c->ev_pnp_done[set], 0));
     return ODO_OK;
 }
 
-// The extraction stream's waits before batch number `bc` (the batch_counter it
-// will have): its frame set is free once the PnP of the batch that last used
-// it is done, and (schedule 5) the PnP of batch bc - pyr_wait is done.
-static int queue_batch_waits(odo_ctx* c, uint64_t bc) {
+// The extraction stream's waits before the next batch: its frame set is free
+// once the PnP of the batch that last used it is done, and the PnP of the
+// batch PYR_WAIT before it is done.
+static int queue_batch_waits(odo_ctx* c) {
     int e;
-    const int s = (int)((c->seq_set + (int)(bc - c->batch_counter) + 1) % NSETS);  // the set batch bc extracts into
+    const int s = next_set(c);
     if (c->pdone_rec[s] && (e = wait_pnp_done(c, c->stream, s))) return e;
-    if (c->sched == 5 && c->pyr_wait > 0 && bc >= (uint64_t)c->pyr_wait) {
-        const int sb = c->batch_set[(bc - (uint64_t)c->pyr_wait) & 7];
-        if (!(ODO_WAIT_DEDUP && sb == s && c->pdone_rec[s]) && (e = wait_pnp_done(c, c->stream, sb))) return e;
-    }
+    // batch b always uses set b % NSETS (seq_set and batch_counter only ever advance together)
+    if (c->batch_counter >= (uint64_t)PYR_WAIT && (e = wait_pnp_done(c, c->stream, (s + NSETS - PYR_WAIT) % NSETS)))
+        return e;
     return ODO_OK;
 }
 
@@ -423,28 +385,6 @@ static int queue_batch_waits(odo_ctx* c, uint64_t bc) {
 // tens of microseconds per mark once several streams are busy.
 static inline void tmark(odo_ctx* c, int i, hipStream_t st) {
     if (c->timing) hipEventRecord(c->ev[i], st);
-}
-
-// Every stream runs at the default priority: measured on MI355X, giving the
-// pair / PnP streams the highest priority starves the extraction stream and
-// costs 17% throughput (1.63 vs 1.35 ms per 64-frame step). ODO_STREAM_PRIO=1
-// restores the high priority for experiments.
-static int pair_stream_priority() {
-    const char* e = odo_knob("ODO_STREAM_PRIO");
-    if (!(e && e[0] == '1')) return 0;
-    int least = 0, greatest = 0;
-    if (hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess) return 0;
-    return greatest;
-}
-
-// ODO_EXTRACT_STREAM_PRIO=1 (tuning): the extraction stream (the step's
-// critical path) at the highest stream priority
-static int extract_stream_priority() {
-    const char* e = odo_knob("ODO_EXTRACT_STREAM_PRIO");
-    if (!(e && e[0] == '1')) return 0;
-    int least = 0, greatest = 0;
-    if (hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess) return 0;
-    return greatest;
 }
 
 // Packed layout in the staging buffer: 256-byte aligned sections
@@ -501,7 +441,7 @@ static void free_ctx(odo_ctx* c) {
     }
     for (auto& P : c->pb) {
         void* pp[] = {P.matches, P.n_matches, P.n_good, P.pair_valid, P.good, P.f2_src, P.best_mask, P.res, P.T12,
-                      P.edges, P.pnp_mask, P.pair_phase};
+                      P.edges, P.pnp_mask};
         for (void* q : pp)
             if (q) hipFree(q);
     }
@@ -512,20 +452,14 @@ static void free_ctx(odo_ctx* c) {
     }
     if (c->kt_ref) hipEventDestroy(c->kt_ref);
     for (int i = 0; i < NSETS; i++) {
-        hipEvent_t* evs[] = {&c->ev_ra[i], &c->ev_rb[i], &c->ev_pa[i], &c->ev_pb[i]};
-        for (hipEvent_t* e : evs)
-            if (*e) hipEventDestroy(*e);
+        if (c->ev_pnp_done[i]) hipEventDestroy(c->ev_pnp_done[i]);
         if (c->ev_xdone[i]) hipEventDestroy(c->ev_xdone[i]);
-        if (c->ev_raw[i]) hipEventDestroy(c->ev_raw[i]);
-        if (c->ev_pyr[i]) hipEventDestroy(c->ev_pyr[i]);
-        if (c->ev_blur[i]) hipEventDestroy(c->ev_blur[i]);
         if (c->ev_geo[i]) hipEventDestroy(c->ev_geo[i]);
     }
     for (int i = 0; i < 2; i++) {
         if (c->ev_in_copied[i]) hipEventDestroy(c->ev_in_copied[i]);
         if (c->ev_in_free[i]) hipEventDestroy(c->ev_in_free[i]);
     }
-    if (c->ev_knn) hipEventDestroy(c->ev_knn);
     if (c->ev_latch) hipEventDestroy(c->ev_latch);
     if (c->ev_depth_done) hipEventDestroy(c->ev_depth_done);
     if (c->stage_h) (void)hipHostFree(c->stage_h);
@@ -995,7 +929,6 @@ static int alloc_buffers(odo_ctx* c) {
         if ((e = dalloc(&P.T12, B * 16))) return e;
         if ((e = dalloc((uint8_t**)&P.edges, B * c->kp_cap * pnp_edge_bytes()))) return e;
         if ((e = dalloc(&P.pnp_mask, B * c->kp_cap))) return e;
-        if ((e = dalloc(&P.pair_phase, B))) return e;
     }
     int pw = 1;
     while (pw < c->kp_cap) pw <<= 1;
@@ -1129,87 +1062,29 @@ odo_ctx* odo_create(const odo_config* cfg, int device) {
     const char* ser = odo_knob("ODO_SERIAL_STREAMS");
     c->serial = ser && ser[0] == '1';
     if (const char* sk = odo_knob("ODO_SKIP")) c->skip = atoi(sk);
-    if (const char* sc = odo_knob("ODO_SCHED")) c->sched = atoi(sc);
-    // only the streams the schedule uses (each extra stream shares one of the
-    // process's GPU_MAX_HW_QUEUES hardware queues with another and serialises
-    // against it); the others alias
-    // ODO_PAIR_CUMASK / ODO_EXTRACT_CUMASK (tuning): comma-separated 32-bit
-    // hex words of a CU mask for the pair / extraction streams (spatial
-    // partitioning of the CUs between the latency-bound pair stages and the
-    // throughput-bound extraction)
-    auto parse_mask = [](const char* e, std::vector<uint32_t>& m) {
-        m.clear();
-        while (e && *e) {
-            char* end = nullptr;
-            m.push_back((uint32_t)strtoul(e, &end, 16));
-            if (end == e) break;
-            e = *end == ',' ? end + 1 : end;
-        }
-        return !m.empty();
-    };
-    std::vector<uint32_t> pmask, xmask;
-    const bool pm = parse_mask(odo_knob("ODO_PAIR_CUMASK"), pmask);
-    const bool xm = parse_mask(odo_knob("ODO_EXTRACT_CUMASK"), xmask);
-    auto mk = [&](hipStream_t* s, bool prio) {
-        bool r;
-        if (prio && pm)
-            r = hipExtStreamCreateWithCUMask(s, (uint32_t)pmask.size(), pmask.data()) == hipSuccess;
-        else if (!prio && xm)
-            r = hipExtStreamCreateWithCUMask(s, (uint32_t)xmask.size(), xmask.data()) == hipSuccess;
-        else if (!prio && s == &c->stream && extract_stream_priority() != 0)
-            r = hipStreamCreateWithPriority(s, hipStreamNonBlocking, extract_stream_priority()) == hipSuccess;
-        else
-            r = prio ? hipStreamCreateWithPriority(s, hipStreamNonBlocking, pair_stream_priority()) == hipSuccess
-                     : hipStreamCreateWithFlags(s, hipStreamNonBlocking) == hipSuccess;
+    // Every stream runs at the default priority: measured on MI355X, giving
+    // the pair streams the highest priority starves the extraction stream and
+    // costs 17% throughput (1.63 vs 1.35 ms per 64-frame step).
+    auto mk = [&](hipStream_t* s) {
+        const bool r = hipStreamCreateWithFlags(s, hipStreamNonBlocking) == hipSuccess;
         if (r) c->owned.push_back(*s);
         return r;
     };
-    bool ok = mk(&c->stream, false);
-    if (ok && c->serial) {
-        c->pstream = c->pstream2 = c->side = c->pnpa = c->pnpb = c->stream;
-    } else if (ok && c->sched == 5) {
-        if (const char* np = odo_knob("ODO_PSTREAMS")) c->npstreams = std::min(3, std::max(1, atoi(np)));
-        if (const char* kp = odo_knob("ODO_KNN_PAIR")) c->knn_pair = atoi(kp) != 0;
-        if (const char* kg = odo_knob("ODO_KNN_GATE")) c->knn_gate = atoi(kg) != 0;
-        if (const char* pw = odo_knob("ODO_PYR_WAIT")) c->pyr_wait = std::min(NSETS - 1, std::max(0, atoi(pw)));
-        ok = mk(&c->pstream, true) && (c->npstreams < 2 || mk(&c->pstream2, true)) &&
-             (c->npstreams < 3 || mk(&c->pstream3, true));
-        if (c->npstreams < 2) c->pstream2 = c->pstream;
-        if (c->npstreams < 3) c->pstream3 = c->pstream;
-        c->side = c->pnpa = c->pnpb = c->pstream;
-        const char* bs = odo_knob("ODO_BLUR_STREAM");
-        if (ok && bs && atoi(bs) != 0) ok = mk(&c->bstream, false);
-    } else if (ok) {
-        ok = mk(&c->pstream, true) && mk(&c->pnpa, true) && (c->sched == 0 || mk(&c->side, false)) &&
-             (c->sched != 1 || mk(&c->pnpb, true));
-        if (c->sched == 0) c->side = c->stream;
-        if (c->sched != 1) c->pnpb = c->pnpa;
-        c->pstream2 = c->pstream;
-    }
-    // The context's events only order its streams against each other (and
-    // tell the host that inputs were consumed): none needs the system-scope
-    // cache writeback + invalidate a default event record performs, which on
-    // this part also disturbs every kernel then running (round 5: ~10 records
-    // per batch; DESIGN §4 Pipelining)
-    const unsigned evf = ODO_SYNC_EVENT_FLAGS;
+    bool ok = mk(&c->stream);
+    if (ok && c->serial)
+        c->pstream = c->pstream2 = c->stream;
+    else if (ok)
+        ok = mk(&c->pstream) && mk(&c->pstream2);
+    const unsigned evf = SYNC_EVENT_FLAGS;
     for (int i = 0; i < NSETS && ok; i++)
-        ok = hipEventCreateWithFlags(&c->ev_ra[i], evf) == hipSuccess &&
-             hipEventCreateWithFlags(&c->ev_rb[i], evf) == hipSuccess &&
-             hipEventCreateWithFlags(&c->ev_pa[i], evf) == hipSuccess &&
-             hipEventCreateWithFlags(&c->ev_pb[i], evf) == hipSuccess;
-    for (int i = 0; i < NSETS && ok; i++)
-        ok = hipEventCreateWithFlags(&c->ev_xdone[i], evf) == hipSuccess &&
-             hipEventCreateWithFlags(&c->ev_raw[i], evf) == hipSuccess &&
-             hipEventCreateWithFlags(&c->ev_pyr[i], evf) == hipSuccess &&
-             hipEventCreateWithFlags(&c->ev_blur[i], evf) == hipSuccess &&
+        ok = hipEventCreateWithFlags(&c->ev_pnp_done[i], evf) == hipSuccess &&
+             hipEventCreateWithFlags(&c->ev_xdone[i], evf) == hipSuccess &&
              hipEventCreateWithFlags(&c->ev_geo[i], evf) == hipSuccess;
-    if (!c->bstream) c->bstream = c->stream;
     if (ok) ok = hipEventCreateWithFlags(&c->ev_latch, evf) == hipSuccess;
     if (ok) ok = hipEventCreateWithFlags(&c->ev_depth_done, evf) == hipSuccess;
-    if (ok) ok = hipEventCreateWithFlags(&c->ev_knn, evf) == hipSuccess;
     // host-input uploads run on their own stream (the DMA engines), ordered
     // against the extraction stream by events only
-    if (ok) ok = mk(&c->cstream, false);
+    if (ok) ok = mk(&c->cstream);
     for (int i = 0; i < 2 && ok; i++)
         ok = hipEventCreateWithFlags(&c->ev_in_copied[i], evf) == hipSuccess &&
              hipEventCreateWithFlags(&c->ev_in_free[i], evf) == hipSuccess;
@@ -1278,8 +1153,8 @@ int odo_set_timing(odo_ctx* c, int mode) {
     c->timing = mode == 1;
     c->ktiming = mode == 2;
     if (c->ktiming) {
-        // timing only: no system-scope fence at the records (see ODO_EVFENCE)
-        const unsigned tf = ODO_EVFENCE == 1 ? hipEventDisableSystemFence : 0u;
+        // timing only: no system-scope fence at the records (see SYNC_EVENT_FLAGS)
+        const unsigned tf = hipEventDisableSystemFence;
         if (!c->kt0[0])
             for (int i = 0; i < odo_ctx::KT_RING; i++)
                 if (hipEventCreateWithFlags(&c->kt0[i], tf) != hipSuccess || hipEventCreateWithFlags(&c->kt1[i], tf) != hipSuccess)
@@ -1390,13 +1265,6 @@ static int run_extract_adaptive(odo_ctx* c, int set, const uint8_t* d_bgr, const
     const size_t nc = (size_t)c->ad_ncells;
     if (d_bgr) launch_gray(st, d_bgr, pyr, c->W, c->H, L0.pitch, (size_t)c->W * c->H * 3, P, n);
     tmark(c, 1, st);
-    const bool split = c->bstream != st;  // blur beside the detector
-    if (split) {
-        HIPCHK(hipEventRecord(c->ev_pyr[set], st));
-        HIPCHK(hipStreamWaitEvent(c->bstream, c->ev_pyr[set], 0));
-        launch_blur(c->bstream, pyr, c->blur + slot * P, P, c->lv, c->lv_h.data(), 1, n);
-        HIPCHK(hipEventRecord(c->ev_blur[set], c->bstream));
-    }
     launch_adapt_smap(st, pyr, P, c->W, c->H, L0.pitch, c->smap, c->smap_stride, n);
     HIPCHK(hipMemsetAsync(c->ahist, 0, (size_t)n * nc * 256 * sizeof(int), st));
     if (c->ad_nbands > 0)
@@ -1409,15 +1277,11 @@ static int run_extract_adaptive(odo_ctx* c, int set, const uint8_t* d_bgr, const
     launch_adapt_assemble(st, c->acell, c->acell_cnt, c->ad_ncells, c->ad_mpc, c->cfg.adaptive.retain_best, c->W,
                           c->H, c->akp, c->kp_cap, c->nkp + slot, c->kp_cap, n);
     tmark(c, 3, st);
-    if (split)
-        HIPCHK(hipStreamWaitEvent(st, c->ev_blur[set], 0));
-    else
-        launch_blur(st, pyr, c->blur + slot * P, P, c->lv, c->lv_h.data(), 1, n);
+    launch_blur(st, pyr, c->blur + slot * P, P, c->lv, c->lv_h.data(), 1, n);
     tmark(c, 4, st);
-    launch_adapt_finalize(st, c->blur + slot * P, P, L0.pitch, c->akp, c->kp_cap, c->nkp + slot, c->a_cos, c->a_sin,
-                          d_depth, (size_t)c->W * c->H, c->W, c->cal, c->kps + slot * c->kp_cap,
-                          c->desc + slot * c->kp_cap * 32, c->kun + slot * c->kp_cap * 2, c->xyz + slot * c->kp_cap * 3,
-                          c->ur + slot * c->kp_cap, c->kp_cap, n);
+    const FrameSlot f = frame_at(c, slot);
+    launch_adapt_finalize(st, c->blur + slot * P, P, L0.pitch, c->akp, c->kp_cap, f.nkp, c->a_cos, c->a_sin, d_depth,
+                          (size_t)c->W * c->H, c->W, c->cal, f.kps, f.desc, f.kun, f.xyz, f.ur, c->kp_cap, n);
     tmark(c, 5, st);
     HIPCHK(hipGetLastError());
     return ODO_OK;
@@ -1452,16 +1316,20 @@ static int run_extract_adaptive_orb(odo_ctx* c, int set, const uint8_t* d_bgr, c
     tmark(c, 3, st);
     launch_blur(st, pyr, c->blur + slot * P, P, c->lv, c->lv_h.data(), OA_NLEV, n);
     tmark(c, 4, st);
+    const FrameSlot f = frame_at(c, slot);
     launch_oa_finalize(st, pyr, c->blur + slot * P, P, c->lv, c->cpyr, c->cp_stride, c->oai, c->oac, c->osc, c->oakp,
-                       c->kp_cap, c->nkp + slot, d_depth, (size_t)c->W * c->H, c->W, c->cal,
-                       c->kps + slot * c->kp_cap, c->desc + slot * c->kp_cap * 32, c->kun + slot * c->kp_cap * 2,
-                       c->xyz + slot * c->kp_cap * 3, c->ur + slot * c->kp_cap, c->kp_cap, n);
+                       c->kp_cap, f.nkp, d_depth, (size_t)c->W * c->H, c->W, c->cal, f.kps, f.desc, f.kun, f.xyz, f.ur,
+                       c->kp_cap, n);
     tmark(c, 5, st);
     HIPCHK(hipGetLastError());
     return ODO_OK;
 }
 
-static int run_extract(odo_ctx* c, int set, const uint8_t* d_bgr, const uint16_t* d_depth, int n, int slot0) {
+// `geometry`: the keypoint geometry (undistort, depth) in the finalize launch;
+// a batch that runs it on its pair stream (track_batch) leaves it out there.
+// The ADAPTIVE extractors always include it.
+static int run_extract(odo_ctx* c, int set, const uint8_t* d_bgr, const uint16_t* d_depth, int n, int slot0,
+                       bool geometry = true) {
     if (c->adaptive_orb) return run_extract_adaptive_orb(c, set, d_bgr, d_depth, n, slot0);
     if (c->adaptive) return run_extract_adaptive(c, set, d_bgr, d_depth, n, slot0);
     hipStream_t st = c->stream;
@@ -1470,13 +1338,6 @@ static int run_extract(odo_ctx* c, int set, const uint8_t* d_bgr, const uint16_t
     uint8_t* pyr = c->pyr + (size_t)slot * P;
     const bool blur_done = build_pyramid(c, st, d_bgr, pyr, n, c->blur + (size_t)slot * P);
     tmark(c, 1, st);
-    const bool split = c->bstream != st && !blur_done;  // blur beside FAST + octree
-    if (split) {
-        HIPCHK(hipEventRecord(c->ev_pyr[set], st));
-        HIPCHK(hipStreamWaitEvent(c->bstream, c->ev_pyr[set], 0));
-        launch_blur(c->bstream, pyr, c->blur + (size_t)slot * P, P, c->lv, c->lv_h.data(), c->nlevels, n);
-        HIPCHK(hipEventRecord(c->ev_blur[set], c->bstream));
-    }
     launch_fast(st, pyr, P, c->fsegs, (int)c->fsegs_h.size(), c->lv, c->cand + (size_t)slot * c->ncells * c->cell_cap,
                 c->cand_cnt + (size_t)slot * c->ncells, c->ncells, c->cell_cap, c->cfg.orb.ini_th_fast,
                 c->cfg.orb.min_th_fast, c->fs_lds, n);
@@ -1487,25 +1348,13 @@ static int run_extract(odo_ctx* c, int set, const uint8_t* d_bgr, const uint16_t
                   c->keys_per_frame, c->okp + (size_t)slot * c->nlevels * c->okp_stride,
                   c->ocnt + (size_t)slot * c->nlevels, c->okp_stride, c->node_cap, n);
     tmark(c, 3, st);
-    if (c->early_waits) {
-        // ODO_EARLY_WAIT: the next batch's frame-set and PYR_WAIT waits, queued
-        // here, ahead of this batch's finalize, instead of between its end and
-        // the next pyramid (their events were recorded by earlier batches)
-        int e;
-        if ((e = queue_batch_waits(c, c->batch_counter + 1))) return e;
-        c->pre_waited = c->batch_counter + 1;
-    }
-    if (split)
-        HIPCHK(hipStreamWaitEvent(st, c->ev_blur[set], 0));
-    else if (!blur_done)
-        launch_blur(st, pyr, c->blur + (size_t)slot * P, P, c->lv, c->lv_h.data(), c->nlevels, n);
+    if (!blur_done) launch_blur(st, pyr, c->blur + (size_t)slot * P, P, c->lv, c->lv_h.data(), c->nlevels, n);
     tmark(c, 4, st);
+    const FrameSlot f = frame_at(c, slot);
     launch_finalize(st, pyr, c->blur + (size_t)slot * P, P, c->lv, c->nlevels,
                     c->okp + (size_t)slot * c->nlevels * c->okp_stride, c->ocnt + (size_t)slot * c->nlevels,
-                    c->okp_stride, d_depth, (size_t)c->W * c->H, c->W, c->cal, c->kps + (size_t)slot * c->kp_cap,
-                    c->desc + (size_t)slot * c->kp_cap * 32, c->kun + (size_t)slot * c->kp_cap * 2,
-                    c->xyz + (size_t)slot * c->kp_cap * 3, c->ur + (size_t)slot * c->kp_cap, c->nkp + slot, c->kp_cap,
-                    n, !c->geo_pair);
+                    c->okp_stride, d_depth, (size_t)c->W * c->H, c->W, c->cal, f.kps, f.desc, f.kun, f.xyz, f.ur, f.nkp,
+                    c->kp_cap, n, geometry);
     tmark(c, 5, st);
     HIPCHK(hipGetLastError());
     return ODO_OK;
@@ -1530,89 +1379,48 @@ int odo_extract_batch(odo_ctx* c, const uint8_t* d_bgr, const uint16_t* d_depth,
     return ODO_OK;
 }
 
-// Pair stages of one batch on the pair stream, over frame set `set`:
+// Pair stages of one batch on its pair stream `st`, over frame set `set`:
 // pair p is (slot p, slot p+1); pair 0 is valid only with a previous frame.
-static int run_pairs(odo_ctx* c, int set, int n) {
-    hipStream_t st = c->cur_p ? c->cur_p : c->pstream;
+// `latched`: the DepthCovariance latch is known to hold its value (track_batch),
+// so the latch kernel is left out. `defer_done`: the caller records the set's
+// PnP-done event itself, after the result copy it queues behind the PnP.
+static int run_pairs(odo_ctx* c, hipStream_t st, int set, int n, bool latched, bool defer_done) {
     auto& P = c->pb[set];
     const size_t KC = (size_t)c->kp_cap;
-    const size_t b = fbase(c, set);
-    uint8_t* desc = c->desc + b * KC * 32;
-    int* nkp = c->nkp + b;
-    float* xyz = c->xyz + b * KC * 3;
+    const FrameSlot f = frame_at(c, fbase(c, set));
     tmark(c, 6, st);
     launch_pair_valid(st, P.pair_valid, n, c->has_prev ? 1 : 0);
-    launch_pair_match(st, c->knn_idx[set], c->knn_dist[set], KC, xyz, nkp, c->kp_cap, 0, c->cfg.nn_ratio,
-                      c->lm_bits[set], c->lm_words, c->knn_split, (size_t)c->maxb * KC, c->cfg.ransac.check_depth, P.matches, P.n_matches, P.good, P.n_good, P.f2_src,
-                      c->sort_scratch, c->match_cap, n);
+    launch_pair_match(st, c->knn_idx[set], c->knn_dist[set], KC, f.xyz, f.nkp, c->kp_cap, 0, c->cfg.nn_ratio,
+                      c->lm_bits[set], c->lm_words, c->knn_split, (size_t)c->maxb * KC, c->cfg.ransac.check_depth,
+                      P.matches, P.n_matches, P.good, P.n_good, P.f2_src, c->sort_scratch, c->match_cap, n);
     // the DepthCovariance latch is taken from the first valid pair ever: with
     // two pair streams, a batch's latch kernel runs after the previous one's
-    // Once the latch holds a value (k_latch's host flag) and the kernel that
-    // set it has completed (ev_latch), the latch kernel is a no-op: it and its
-    // two ordering packets are left out (ODO_WAIT_DEDUP)
-    if (!c->latched) {
-        if (c->sched == 5 && c->latch_rec) HIPCHK(hipStreamWaitEvent(st, c->ev_latch, 0));
-        launch_latch(st, c->latch, P.good, P.n_good, P.n_matches, P.matches, xyz, c->kp_cap, 0, n, c->match_cap,
+    // (ev_latch). Once the latch holds a value (k_latch's host flag) and the
+    // kernel that set it has completed, the latch kernel is a no-op: it and
+    // its two ordering packets are left out
+    if (!latched) {
+        if (c->latch_rec) HIPCHK(hipStreamWaitEvent(st, c->ev_latch, 0));
+        launch_latch(st, c->latch, P.good, P.n_good, P.n_matches, P.matches, f.xyz, c->kp_cap, 0, n, c->match_cap,
                      c->cfg.ransac.min_inlier_th, c->cfg.ransac.sample_size, c->cfg.ransac.iterations, P.pair_valid,
                      c->latch_set_h);
-        if (c->sched == 5) {
-            HIPCHK(hipEventRecord(c->ev_latch, st));
-            c->latch_rec = true;
-        }
+        HIPCHK(hipEventRecord(c->ev_latch, st));
+        c->latch_rec = true;
     }
     tmark(c, 7, st);
-    if (c->sched != 1) {
-        // both RANSAC launches on the pair stream, then one PnP launch for the
-        // whole batch on its own stream (the pair stream moves on to the next
-        // batch while it runs)
-        if (!(c->skip & 16))
-        launch_ransac(st, P.good, P.n_good, P.n_matches, P.matches, xyz, c->kp_cap, 0, c->match_cap, c->rcfg,
+    // RANSAC, then one PnP launch for the whole batch, back to back on the
+    // batch's own pair stream: nothing else waits for RANSAC alone, so no
+    // marker packet sits between the two launches
+    if (!(c->skip & 16))
+        launch_ransac(st, P.good, P.n_good, P.n_matches, P.matches, f.xyz, c->kp_cap, 0, c->match_cap, c->rcfg,
                       c->latch, P.pair_valid, 20, nullptr, c->rscr[set], P.best_mask, c->mask_words, P.res, P.T12, n,
-                      0, P.pair_phase, c->h_open + set);
-        tmark(c, 8, st);
-        // schedule 5: PnP follows RANSAC on the batch's own pair stream, and
-        // nothing waits on ev_rb (the side stream of schedules 0-3 does): no
-        // marker packet between the RANSAC and PnP launches (ODO_WAIT_DEDUP)
-        if (!(ODO_WAIT_DEDUP && c->sched == 5)) HIPCHK(hipEventRecord(c->ev_rb[set], st));
-        hipStream_t ps = c->sched == 5 ? st : c->pnpa;
-        if (ps != st) HIPCHK(hipStreamWaitEvent(ps, c->ev_rb[set], 0));
-        if (!(c->skip & 1))
-            launch_pnp(ps, P.f2_src, xyz, c->kun + b * KC * 2, c->ur + b * KC, nkp, c->kp_cap, 0, c->cal, P.T12,
-                       P.pair_valid, P.n_matches, 20, P.edges, P.res, P.pnp_mask, n);
-        tmark(c, 9, ps);
-        // schedule 5 waits on ev_pb alone (wait_pnp_done), and an async batch
-        // records it again after its result copy, before anything waits on it
-        if (!(ODO_WAIT_DEDUP && c->sched == 5)) HIPCHK(hipEventRecord(c->ev_pa[set], ps));
-        if (!(ODO_WAIT_DEDUP && c->sched == 5 && c->defer_pdone)) HIPCHK(hipEventRecord(c->ev_pb[set], ps));
-        c->pdone_st[set] = ps;
-        HIPCHK(hipGetLastError());
-        return ODO_OK;
-    }
-    // RANSAC part 1 (prep + first eval launch) finishes most pairs; their PnP
-    // starts on its own stream while part 2 evaluates the long pairs, whose
-    // PnP runs on a second stream so the pair stream moves on to the next batch
-    launch_ransac(st, P.good, P.n_good, P.n_matches, P.matches, xyz, c->kp_cap, 0, c->match_cap, c->rcfg, c->latch,
-                  P.pair_valid, 20, nullptr, c->rscr[set], P.best_mask, c->mask_words, P.res, P.T12, n, 1,
-                  P.pair_phase);
-    HIPCHK(hipEventRecord(c->ev_ra[set], st));
-    HIPCHK(hipStreamWaitEvent(c->pnpa, c->ev_ra[set], 0));
-    if (!(c->skip & 1))
-    launch_pnp(c->pnpa, P.f2_src, xyz, c->kun + b * KC * 2, c->ur + b * KC, nkp, c->kp_cap, 0, c->cal, P.T12,
-               P.pair_valid, P.n_matches, 20, P.edges, P.res, P.pnp_mask, n, P.pair_phase, 1);
-    HIPCHK(hipEventRecord(c->ev_pa[set], c->pnpa));
-    if (!(c->skip & 2))
-    launch_ransac(st, P.good, P.n_good, P.n_matches, P.matches, xyz, c->kp_cap, 0, c->match_cap, c->rcfg, c->latch,
-                  P.pair_valid, 20, nullptr, c->rscr[set], P.best_mask, c->mask_words, P.res, P.T12, n, 2,
-                  P.pair_phase, c->h_open + set);
+                      c->h_open + set);
     tmark(c, 8, st);
-    HIPCHK(hipEventRecord(c->ev_rb[set], st));
-    HIPCHK(hipStreamWaitEvent(c->pnpb, c->ev_rb[set], 0));
     if (!(c->skip & 1))
-    launch_pnp(c->pnpb, P.f2_src, xyz, c->kun + b * KC * 2, c->ur + b * KC, nkp, c->kp_cap, 0, c->cal, P.T12,
-               P.pair_valid, P.n_matches, 20, P.edges, P.res, P.pnp_mask, n, P.pair_phase, 0);
-    tmark(c, 9, c->pnpb);
-    HIPCHK(hipEventRecord(c->ev_pb[set], c->pnpb));
-    c->pdone_st[set] = nullptr;  // two streams: wait on both events
+        launch_pnp(st, P.f2_src, f.xyz, f.kun, f.ur, f.nkp, c->kp_cap, 0, c->cal, P.T12, P.pair_valid, P.n_matches, 20,
+                   P.edges, P.res, P.pnp_mask, n);
+    tmark(c, 9, st);
+    if (!defer_done) HIPCHK(hipEventRecord(c->ev_pnp_done[set], st));
+    c->pdone_st[set] = st;
     HIPCHK(hipGetLastError());
     return ODO_OK;
 }
@@ -1646,170 +1454,129 @@ static int finish_batch(odo_ctx* c, int set, int n, odo_pair_result* h_results) 
     return ODO_OK;
 }
 
-int odo_track_batch(odo_ctx* c, const uint8_t* d_bgr, const uint16_t* d_depth, int n, odo_pair_result* h_results) {
-    if (!c || !d_bgr || !d_depth || n <= 0 || n > c->maxb) return fail(ODO_ERR_ARG, "bad track args");
+// The previous batch's last frame into slot 0 of set `s`
+// (Tracking::mLastFrame) on stream `st`, after that batch's geometry when it
+// ran on its pair stream.
+static int roll_last_frame(odo_ctx* c, hipStream_t st, int s) {
+    if (c->geo_rec[c->seq_set]) HIPCHK(hipStreamWaitEvent(st, c->ev_geo[c->seq_set], 0));
+    const FrameSlot src = frame_at(c, fbase(c, c->seq_set) + c->seq_n), dst = frame_at(c, fbase(c, s));
+    launch_copy_frame(st, src.kps, src.desc, src.kun, src.xyz, src.ur, src.nkp, dst.kps, dst.desc, dst.kun, dst.xyz,
+                      dst.ur, dst.nkp, c->kp_cap);
+    return ODO_OK;
+}
+
+// The kNN-2 launch of the n pairs of set `s`, in the context's kernel form
+static void launch_set_knn2(odo_ctx* c, hipStream_t st, int s, int n) {
+    const size_t KC = (size_t)c->kp_cap;
+    const FrameSlot f = frame_at(c, fbase(c, s));
+    if (c->knn_mx)
+        launch_knn2_mx(st, f.desc, f.nkp, KC * 32, f.desc + KC * 32, f.nkp + 1, KC * 32, c->knn_idx[s], c->knn_dist[s],
+                       KC, c->kp_cap, n, c->qlist[s], c->qcnt[s], KC, c->knn_mx);
+    else
+        launch_knn2(st, f.desc, f.nkp, KC * 32, f.desc + KC * 32, f.nkp + 1, KC * 32, c->knn_idx[s], c->knn_dist[s],
+                    KC, c->kp_cap, n, c->qlist[s], c->qcnt[s], KC, c->knn_split, (size_t)c->maxb * KC);
+}
+
+// kNN-2 of the batch's pairs on stream `st` (an event pair around it in timing mode 2)
+static int run_knn(odo_ctx* c, hipStream_t st, int s, int n) {
+    const FrameSlot f = frame_at(c, fbase(c, s));
+    // the query frames' VO landmarks first: kNN-2 runs on their keypoints only
+    const float mThDepth = c->cfg.calib.mbf * c->cfg.calib.th_depth / c->cfg.calib.fx;
+    launch_vo_lm(st, f.xyz, f.nkp, c->kp_cap, 0, mThDepth, c->lm_bits[s], c->lm_words, c->qlist[s], c->qcnt[s], n);
+    int kt = -1;
+    if (c->ktiming) {
+        kt = c->kt_next;
+        if (c->kt_pending == odo_ctx::KT_RING) {  // slot reused: fold its time first
+            int e;
+            if ((e = kt_collect(c, kt))) return e;
+            c->kt_pending--;
+        }
+        HIPCHK(hipEventRecord(c->kt0[kt], st));
+    }
+    c->last_knn_set = s;  // odo_knn_replay_time
+    c->last_knn_n = n;
+    if (!(c->skip & 8)) launch_set_knn2(c, st, s, n);
+    if (kt >= 0) {
+        HIPCHK(hipEventRecord(c->kt1[kt], st));
+        c->kt_next = (kt + 1) % odo_ctx::KT_RING;
+        c->kt_pending++;
+    }
+    tmark(c, 10, st);
+    return ODO_OK;
+}
+
+// What differs between the callers of track_batch
+struct BatchOpts {
+    // a track_host batch: its depth reads must stay on the extraction stream
+    // (ev_in_free, ev_depth_done)
+    bool host_call = false;
+    // the caller queues the result copy on the batch's pair stream
+    // (*pair_stream) and records the set's PnP-done event after it
+    bool defer_results = false;
+};
+
+// Queue one batch (arguments checked by the callers). No host sync.
+static int track_batch(odo_ctx* c, const uint8_t* d_bgr, const uint16_t* d_depth, int n, const BatchOpts& opts,
+                       hipStream_t* pair_stream = nullptr) {
     int e;
-    // decided before this call queues anything: a not-ready query leaves
-    // hipErrorNotReady as the thread's last error, cleared here
-    c->latched = false;
-    if (ODO_WAIT_DEDUP && c->sched == 5 && c->latch_rec && __atomic_load_n(c->latch_set_h, __ATOMIC_ACQUIRE) != 0) {
+    // ---- 1. has the latch its value? Decided before this call queues
+    // anything: a not-ready query leaves hipErrorNotReady as the thread's last
+    // error, cleared here
+    bool latched = false;
+    if (c->latch_rec && __atomic_load_n(c->latch_set_h, __ATOMIC_ACQUIRE) != 0) {
         const hipError_t q = hipEventQuery(c->ev_latch);
-        if (q == hipSuccess) c->latched = true;
+        if (q == hipSuccess) latched = true;
         else if (q == hipErrorNotReady) (void)hipGetLastError();
         else return fail(ODO_ERR_DEVICE, std::string("hipEventQuery: ") + hipGetErrorString(q));
     }
     const int s = next_set(c);
-    const size_t KC = (size_t)c->kp_cap;
-    // ---- extraction stream: set s is free once the pair stages of the batch
-    // before the previous one (which read it) are done
-    if (c->pre_waited != c->batch_counter && (e = queue_batch_waits(c, c->batch_counter))) return e;
-    if (c->knn_gate && c->knn_rec) HIPCHK(hipStreamWaitEvent(c->stream, c->ev_knn, 0));
+    // ---- 2. extraction stream: set s is free, batch b - PYR_WAIT is done
+    if ((e = queue_batch_waits(c))) return e;
     tmark(c, 0, c->stream);
-    // (the next batch's roll reads this set's last frame on its pair stream,
-    // before its PnP: the batch that reuses this set waits for that PnP
-    // through PYR_WAIT, which therefore has to lie in [1, NSETS - 1])
-    const bool geo_pair = ODO_GEO_PAIR && c->sched == 5 && c->knn_pair && !c->adaptive && !c->adaptive_orb &&
-                          !c->timing && !c->host_call && c->ev_geo[0] && c->pyr_wait >= 1 &&
-                          c->pyr_wait <= NSETS - 1;
-    if (c->has_prev && !geo_pair) {
-        // the previous batch's last frame becomes slot 0 (Tracking::mLastFrame);
-        // its geometry ran on that batch's pair stream when it took that path
-        if (c->geo_rec[c->seq_set]) HIPCHK(hipStreamWaitEvent(c->stream, c->ev_geo[c->seq_set], 0));
-        const size_t src = fbase(c, c->seq_set) + c->seq_n, dst = fbase(c, s);
-        launch_copy_frame(c->stream, c->kps + src * KC, c->desc + src * KC * 32, c->kun + src * KC * 2,
-                          c->xyz + src * KC * 3, c->ur + src * KC, c->nkp + src, c->kps + dst * KC,
-                          c->desc + dst * KC * 32, c->kun + dst * KC * 2, c->xyz + dst * KC * 3, c->ur + dst * KC,
-                          c->nkp + dst, c->kp_cap);
-    }
+    // device inputs: the keypoint geometry (undistort, depth) and the slot-0
+    // roll run at the head of the batch's pair stream instead of at the end of
+    // the extraction stream, the step's critical path (round 6: 152.0-152.6 vs
+    // 150.9-151.3 k frames/s, three alternations on one box, profiles/r06_d).
+    // Not for the ADAPTIVE extractors (geometry inside their finalize), stage
+    // timing (marks per stream) and host inputs.
+    const bool geo_pair = !c->adaptive && !c->adaptive_orb && !c->timing && !opts.host_call;
+    // ---- 3. the roll
+    if (c->has_prev && !geo_pair && (e = roll_last_frame(c, c->stream, s))) return e;
+    // ---- 4. extraction
     // (Round 6 measured ev_xdone completed by the last extraction kernel,
     // hipExtLaunchKernel's stop event, instead of a marker packet: with the
     // runtime's worker-thread dispatch the pair stream's wait on it did not
     // always hold (a batch's kNN-2 started before the previous batch's, seen
     // in the step marks), and the step was no faster. Not kept.)
-    c->geo_pair = geo_pair;  // run_extract leaves the geometry out (only for this call)
-    c->early_waits = ODO_EARLY_WAIT && c->sched == 5 && !c->adaptive && !c->adaptive_orb;
-    e = run_extract(c, s, d_bgr, d_depth, n, 1);
-    c->geo_pair = false;
-    c->early_waits = false;
-    if (e) return e;
-    // the kNN-2 stream: the extraction stream, or the side stream (sched 3)
-    hipStream_t ks = c->stream;
-    if (c->sched == 3) {
-        // side stream: the rand() words first (seed-only, they overlap the
-        // extraction), then kNN-2 once the batch's descriptors exist
-        if (c->pdone_rec[s]) HIPCHK(hipStreamWaitEvent(c->side, c->ev_rb[s], 0));
-        launch_ransac_raw(c->side, c->rscr[s], n, c->match_cap, c->mask_words, c->rcfg, (uint64_t)c->cfg.seed,
-                          c->pair_counter, nullptr);
-        HIPCHK(hipEventRecord(c->ev_xdone[s], c->stream));
-        HIPCHK(hipStreamWaitEvent(c->side, c->ev_xdone[s], 0));
-        ks = c->side;
-    }
-    // kNN-2 of the batch's pairs on stream ks (event pair around it in timing mode 2)
-    auto knn_on = [&](hipStream_t kst) -> int {
-        const size_t b = fbase(c, s);
-        uint8_t* desc = c->desc + b * KC * 32;
-        int* nkp = c->nkp + b;
-        // the query frames' VO landmarks first: kNN-2 runs on their keypoints only
-        const float mThDepth = c->cfg.calib.mbf * c->cfg.calib.th_depth / c->cfg.calib.fx;
-        launch_vo_lm(kst, c->xyz + b * KC * 3, nkp, c->kp_cap, 0, mThDepth, c->lm_bits[s], c->lm_words, c->qlist[s],
-                     c->qcnt[s], n);
-        int kt = -1;
-        if (c->ktiming) {
-            kt = c->kt_next;
-            if (c->kt_pending == odo_ctx::KT_RING) {  // slot reused: fold its time first
-                int e2;
-                if ((e2 = kt_collect(c, kt))) return e2;
-                c->kt_pending--;
-            }
-            HIPCHK(hipEventRecord(c->kt0[kt], kst));
-        }
-        c->last_knn_set = s;  // odo_knn_replay_time
-        c->last_knn_n = n;
-        if (!(c->skip & 8)) {
-            if (c->knn_mx)
-                launch_knn2_mx(kst, desc, nkp, KC * 32, desc + KC * 32, nkp + 1, KC * 32, c->knn_idx[s], c->knn_dist[s],
-                               KC, c->kp_cap, n, c->qlist[s], c->qcnt[s], KC, c->knn_mx);
-            else
-                launch_knn2(kst, desc, nkp, KC * 32, desc + KC * 32, nkp + 1, KC * 32, c->knn_idx[s], c->knn_dist[s],
-                            KC, c->kp_cap, n, c->qlist[s], c->qcnt[s], KC, c->knn_split, (size_t)c->maxb * KC);
-        }
-        if (kt >= 0) {
-            HIPCHK(hipEventRecord(c->kt1[kt], kst));
-            c->kt_next = (kt + 1) % odo_ctx::KT_RING;
-            c->kt_pending++;
-        }
-        tmark(c, 10, kst);
-        if (c->knn_gate) {
-            HIPCHK(hipEventRecord(c->ev_knn, kst));
-            c->knn_rec = true;
-        }
-        return ODO_OK;
-    };
-    // schedule 5 runs kNN-2 at the head of the batch's pair stream (the
-    // extraction stream, the critical one, goes on to the next batch)
-    const bool knn_pair = c->sched == 5 && c->knn_pair;
-    if (!knn_pair && (e = knn_on(ks))) return e;
-    if (c->sched == 3) {
-        HIPCHK(hipEventRecord(c->ev_raw[s], c->side));
-        HIPCHK(hipEventRecord(c->ev_xdone[s], c->side));
-    } else if (c->sched == 0) {
-        // RANSAC's rand() words (seed-only) at the end of the extraction
-        // stream: set s was released (ev_pa/ev_pb) before this batch began
-        launch_ransac_raw(c->stream, c->rscr[s], n, c->match_cap, c->mask_words, c->rcfg, (uint64_t)c->cfg.seed,
-                          c->pair_counter, nullptr);
-        HIPCHK(hipEventRecord(c->ev_xdone[s], c->stream));
-        HIPCHK(hipEventRecord(c->ev_raw[s], c->stream));
-    } else if (c->sched == 4 || c->sched == 5) {
-        // the words at the head of the batch's pair stream; schedule 5
-        // alternates two pair streams (each also runs its batch's PnP), so one
-        // batch's long RANSAC / PnP overlaps the next batch's pair stages
-        if (c->sched == 5) {
-            const int q = (int)(c->batch_counter % (uint64_t)c->npstreams);
-            c->cur_p = q == 0 ? c->pstream : (q == 1 ? c->pstream2 : c->pstream3);
-        } else {
-            c->cur_p = c->pstream;
-        }
-        if (c->pdone_rec[s] && (e = wait_pnp_done(c, c->cur_p, s))) return e;
-        HIPCHK(hipEventRecord(c->ev_xdone[s], c->stream));
-        launch_ransac_raw(c->cur_p, c->rscr[s], n, c->match_cap, c->mask_words, c->rcfg, (uint64_t)c->cfg.seed,
-                          c->pair_counter, nullptr);
-        // the words and their reader share the stream: no marker (ODO_WAIT_DEDUP)
-        if (!ODO_WAIT_DEDUP) HIPCHK(hipEventRecord(c->ev_raw[s], c->cur_p));
-    } else {
-        HIPCHK(hipEventRecord(c->ev_xdone[s], c->stream));
-        // ---- side stream: RANSAC's rand() words depend on the pair seeds only
-        if (c->pdone_rec[s]) HIPCHK(hipStreamWaitEvent(c->side, c->ev_rb[s], 0));
-        launch_ransac_raw(c->side, c->rscr[s], n, c->match_cap, c->mask_words, c->rcfg, (uint64_t)c->cfg.seed,
-                          c->pair_counter, nullptr);
-        HIPCHK(hipEventRecord(c->ev_raw[s], c->side));
-    }
-    // ---- pair stream
-    if (c->sched != 4 && c->sched != 5) c->cur_p = c->pstream;
-    HIPCHK(hipStreamWaitEvent(c->cur_p, c->ev_xdone[s], 0));
-    if (!(ODO_WAIT_DEDUP && (c->sched == 4 || c->sched == 5))) HIPCHK(hipStreamWaitEvent(c->cur_p, c->ev_raw[s], 0));
+    if ((e = run_extract(c, s, d_bgr, d_depth, n, 1, !geo_pair))) return e;
+    // ---- 5. head of the batch's pair stream. The two pair streams take
+    // alternate batches, so one batch's long RANSAC / PnP overlaps the next
+    // batch's pair stages. RANSAC's rand() words depend on the pair seeds
+    // only: they are queued ahead of the wait for the extraction, on the
+    // stream that reads them (no marker in between).
+    hipStream_t ps = (c->batch_counter & 1) ? c->pstream2 : c->pstream;
+    if (pair_stream) *pair_stream = ps;
+    if (c->pdone_rec[s] && (e = wait_pnp_done(c, ps, s))) return e;
+    HIPCHK(hipEventRecord(c->ev_xdone[s], c->stream));
+    launch_ransac_raw(ps, c->rscr[s], n, c->match_cap, c->mask_words, c->rcfg, (uint64_t)c->cfg.seed, c->pair_counter,
+                      nullptr);
+    HIPCHK(hipStreamWaitEvent(ps, c->ev_xdone[s], 0));
     if (geo_pair) {
-        // the roll (the previous batch's last frame into slot 0, once that
-        // batch's geometry is done) and this batch's geometry, ahead of kNN-2
-        const size_t b = fbase(c, s);
-        if (c->has_prev) {
-            const size_t src = fbase(c, c->seq_set) + c->seq_n, dst = b;
-            if (c->geo_rec[c->seq_set]) HIPCHK(hipStreamWaitEvent(c->cur_p, c->ev_geo[c->seq_set], 0));
-            launch_copy_frame(c->cur_p, c->kps + src * KC, c->desc + src * KC * 32, c->kun + src * KC * 2,
-                              c->xyz + src * KC * 3, c->ur + src * KC, c->nkp + src, c->kps + dst * KC,
-                              c->desc + dst * KC * 32, c->kun + dst * KC * 2, c->xyz + dst * KC * 3, c->ur + dst * KC,
-                              c->nkp + dst, c->kp_cap);
-        }
-        launch_kp_geometry(c->cur_p, c->kps + (b + 1) * KC, c->nkp + b + 1, d_depth, (size_t)c->W * c->H, c->W, c->cal,
-                           c->kun + (b + 1) * KC * 2, c->xyz + (b + 1) * KC * 3, c->ur + (b + 1) * KC, c->kp_cap, n);
-        HIPCHK(hipEventRecord(c->ev_geo[s], c->cur_p));
-        c->geo_rec[s] = true;
-    } else {
-        c->geo_rec[s] = false;
+        if (c->has_prev && (e = roll_last_frame(c, ps, s))) return e;
+        const FrameSlot f = frame_at(c, fbase(c, s) + 1);
+        launch_kp_geometry(ps, f.kps, f.nkp, d_depth, (size_t)c->W * c->H, c->W, c->cal, f.kun, f.xyz, f.ur, c->kp_cap,
+                           n);
+        HIPCHK(hipEventRecord(c->ev_geo[s], ps));
     }
-    if (knn_pair && (e = knn_on(c->cur_p))) return e;
+    c->geo_rec[s] = geo_pair;
+    // kNN-2 here and not on the extraction stream, the critical one, which
+    // goes on to the next batch
+    if ((e = run_knn(c, ps, s, n))) return e;
+    // ---- 6. pair stages
     c->valid_h.assign(n, 1);
     c->valid_h[0] = c->has_prev ? 1 : 0;
-    if (!(c->skip & 4) && (e = run_pairs(c, s, n))) return e;
+    if (!(c->skip & 4) && (e = run_pairs(c, ps, s, n, latched, opts.defer_results))) return e;
+    // ---- 7. bookkeeping
     c->pdone_rec[s] = true;
     c->seq_set = s;
     c->seq_n = n;
@@ -1817,36 +1584,46 @@ int odo_track_batch(odo_ctx* c, const uint8_t* d_bgr, const uint16_t* d_depth, i
     c->last_n = n;
     c->has_prev = true;
     c->pair_counter += (uint64_t)n;
-    c->batch_set[c->batch_counter & 7] = s;
     c->batch_counter++;
-    if ((e = finish_batch(c, s, n, h_results))) return e;
     return ODO_OK;
 }
 
-// odo_track_batch with the result records copied into page-locked host memory
+// track_batch with the result records copied into page-locked host memory
 // asynchronously (on the batch's pair stream, after its PnP): no host sync, so
 // batches keep streaming; the records are valid after odo_synchronize().
-int odo_track_batch_async(odo_ctx* c, const uint8_t* d_bgr, const uint16_t* d_depth, int n, odo_pair_result* h_results) {
-    if (!h_results) return fail(ODO_ERR_ARG, "null results");
-    const int first_valid = c && c->has_prev ? 1 : 0;
+static int track_batch_async(odo_ctx* c, const uint8_t* d_bgr, const uint16_t* d_depth, int n,
+                             odo_pair_result* h_results, bool host_call) {
+    const int first_valid = c->has_prev ? 1 : 0;
+    BatchOpts opts;
+    opts.host_call = host_call;
+    opts.defer_results = true;
+    hipStream_t st = nullptr;  // the batch's pair stream (its PnP ran there last)
     int e;
-    c->defer_pdone = true;  // the PnP-done events are recorded after the copy below
-    e = odo_track_batch(c, d_bgr, d_depth, n, nullptr);
-    c->defer_pdone = false;
-    if (e) return e;
+    if ((e = track_batch(c, d_bgr, d_depth, n, opts, &st))) return e;
     const int s = c->view_set;
     auto& P = c->pb[s];
-    hipStream_t st = c->cur_p ? c->cur_p : c->pstream;  // the batch's pair stream (its PnP ran there last)
     if ((e = wait_pnp_done(c, st, s))) return e;
     hipLaunchKernelGGL(k_res_patch, dim3((n + 255) / 256), dim3(256), 0, st, P.res, P.n_matches, c->qcnt[s], n,
                        first_valid);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(h_results, P.res, (size_t)n * sizeof(odo_pair_result), hipMemcpyDeviceToHost, st));
-    // the batch that next reuses set s waits for these events: include the copy
-    if (!(ODO_WAIT_DEDUP && c->sched == 5)) HIPCHK(hipEventRecord(c->ev_pa[s], st));
-    HIPCHK(hipEventRecord(c->ev_pb[s], st));
+    // the batch that next reuses set s waits for this event: include the copy
+    HIPCHK(hipEventRecord(c->ev_pnp_done[s], st));
     c->pdone_st[s] = st;
     return ODO_OK;
+}
+
+int odo_track_batch(odo_ctx* c, const uint8_t* d_bgr, const uint16_t* d_depth, int n, odo_pair_result* h_results) {
+    if (!c || !d_bgr || !d_depth || n <= 0 || n > c->maxb) return fail(ODO_ERR_ARG, "bad track args");
+    int e;
+    if ((e = track_batch(c, d_bgr, d_depth, n, BatchOpts{}))) return e;
+    return finish_batch(c, c->view_set, n, h_results);
+}
+
+int odo_track_batch_async(odo_ctx* c, const uint8_t* d_bgr, const uint16_t* d_depth, int n, odo_pair_result* h_results) {
+    if (!h_results) return fail(ODO_ERR_ARG, "null results");
+    if (!c || !d_bgr || !d_depth || n <= 0 || n > c->maxb) return fail(ODO_ERR_ARG, "bad track args");
+    return track_batch_async(c, d_bgr, d_depth, n, h_results, false);
 }
 
 // Position the sequence (SURVEY §8(e) frames mode): the next batch's pair p
@@ -1899,10 +1676,10 @@ static int track_host(odo_ctx* c, const uint8_t* bgr, const uint16_t* depth, int
     int e = ODO_OK;
     if (hipStreamWaitEvent(c->stream, c->ev_in_copied[k], 0) != hipSuccess) e = fail(ODO_ERR_DEVICE, "hipStreamWaitEvent");
     const uint16_t* dd = sparse ? (const uint16_t*)dmap : c->depth_in[k];
-    c->host_call = true;  // the batch's depth reads stay on the extraction stream (ev_in_free, ev_depth_done)
-    if (!e) e = async_res ? odo_track_batch_async(c, c->bgr_in[k], dd, n, async_res)
-                          : odo_track_batch(c, c->bgr_in[k], dd, n, nullptr);
-    c->host_call = false;
+    BatchOpts opts;
+    opts.host_call = true;
+    if (!e) e = async_res ? track_batch_async(c, c->bgr_in[k], dd, n, async_res, true)
+                          : track_batch(c, c->bgr_in[k], dd, n, opts);
     if (!e) {
         // everything that reads staging buffer k (and a sparse batch's depth
         // frames) is queued on the extraction stream
@@ -1976,7 +1753,7 @@ int odo_get_frame(odo_ctx* c, int i, orb_kp* kps, uint8_t* desc, float* kps_un, 
     int e;
     if ((e = sync_all(c))) return e;
     // frame i of the last batch: slot i+1 of its frame set
-    const size_t slot = fbase(c, c->view_set) + i + 1;
+    const FrameSlot f = frame_at(c, fbase(c, c->view_set) + i + 1);
     // every array at its full capacity (no round trip for the count first):
     // async copies into the pinned staging buffer, one sync, then the
     // caller's buffers
@@ -1987,12 +1764,12 @@ int odo_get_frame(odo_ctx* c, int i, orb_kp* kps, uint8_t* desc, float* kps_un, 
     if ((e = stage_reserve(c, pk.off))) return e;
     uint8_t* h = c->stage_h;
     hipStream_t st = c->stream;
-    HIPCHK(hipMemcpyAsync(h + o_n, c->nkp + slot, sizeof(int), hipMemcpyDeviceToHost, st));
-    if (kps) HIPCHK(hipMemcpyAsync(h + o_k, c->kps + slot * KC, KC * sizeof(orb_kp), hipMemcpyDeviceToHost, st));
-    if (desc) HIPCHK(hipMemcpyAsync(h + o_d, c->desc + slot * KC * 32, KC * 32, hipMemcpyDeviceToHost, st));
-    if (kps_un) HIPCHK(hipMemcpyAsync(h + o_u, c->kun + slot * KC * 2, KC * 8, hipMemcpyDeviceToHost, st));
-    if (xyz) HIPCHK(hipMemcpyAsync(h + o_x, c->xyz + slot * KC * 3, KC * 12, hipMemcpyDeviceToHost, st));
-    if (u_right) HIPCHK(hipMemcpyAsync(h + o_r, c->ur + slot * KC, KC * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(h + o_n, f.nkp, sizeof(int), hipMemcpyDeviceToHost, st));
+    if (kps) HIPCHK(hipMemcpyAsync(h + o_k, f.kps, KC * sizeof(orb_kp), hipMemcpyDeviceToHost, st));
+    if (desc) HIPCHK(hipMemcpyAsync(h + o_d, f.desc, KC * 32, hipMemcpyDeviceToHost, st));
+    if (kps_un) HIPCHK(hipMemcpyAsync(h + o_u, f.kun, KC * 8, hipMemcpyDeviceToHost, st));
+    if (xyz) HIPCHK(hipMemcpyAsync(h + o_x, f.xyz, KC * 12, hipMemcpyDeviceToHost, st));
+    if (u_right) HIPCHK(hipMemcpyAsync(h + o_r, f.ur, KC * 4, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     int cnt = 0;
     memcpy(&cnt, h + o_n, sizeof(int));
@@ -2015,7 +1792,7 @@ int odo_get_pair(odo_ctx* c, int i, odo_dmatch* matches, int match_cap, int* n_m
     auto& P = c->pb[c->view_set];
     HIPCHK(hipMemcpy(&nm, P.n_matches + i, sizeof(int), hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(&ng, P.n_good + i, sizeof(int), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(&n2, c->nkp + fbase(c, c->view_set) + i + 1, sizeof(int), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&n2, frame_at(c, fbase(c, c->view_set) + i + 1).nkp, sizeof(int), hipMemcpyDeviceToHost));
     if (n_matches) *n_matches = nm;
     if (n_good) *n_good = ng;
     std::vector<odo_dmatch> M(std::max(nm, 1));
@@ -2133,18 +1910,8 @@ int odo_knn_replay_time(odo_ctx* c, int reps, float* avg_ms) {
         return fail(ODO_ERR_DEVICE, std::string("knn_replay_time: HIP error pending from an earlier call: ") +
                                         hipGetErrorString(pending));
     const int s = c->last_knn_set, n = c->last_knn_n;
-    const size_t b = fbase(c, s), KC = (size_t)c->kp_cap;
-    uint8_t* desc = c->desc + b * KC * 32;
-    int* nkp = c->nkp + b;
     hipStream_t st = c->stream;
-    auto launch = [&]() {
-        if (c->knn_mx)
-            launch_knn2_mx(st, desc, nkp, KC * 32, desc + KC * 32, nkp + 1, KC * 32, c->knn_idx[s], c->knn_dist[s], KC,
-                           c->kp_cap, n, c->qlist[s], c->qcnt[s], KC, c->knn_mx);
-        else
-            launch_knn2(st, desc, nkp, KC * 32, desc + KC * 32, nkp + 1, KC * 32, c->knn_idx[s], c->knn_dist[s], KC,
-                        c->kp_cap, n, c->qlist[s], c->qcnt[s], KC, c->knn_split, (size_t)c->maxb * KC);
-    };
+    auto launch = [&]() { launch_set_knn2(c, st, s, n); };
     hipEvent_t e0, e1;
     HIPCHK(hipEventCreate(&e0));
     HIPCHK(hipEventCreate(&e1));
@@ -2243,7 +2010,7 @@ int odo_last_timings(odo_ctx* c, float* ms, int cap, const char** names) {
     static const char* kNamesAd[] = {"gray", "smap+cand", "chain+select", "blur", "finalize", "knn2", "match+sort",
                                      "ransac", "pnp"};
     const char* const* kNames = c && c->adaptive ? kNamesAd : kNamesOrb;
-    // stage i spans events (a[i], b[i]): extraction stream 0..5,10; pair stream 6..9
+    // stage i spans events (a[i], b[i]): extraction stream 0..5; pair stream 10, 6..9
     static const int a[9] = {0, 1, 2, 3, 4, 5, 6, 7, 8}, b[9] = {1, 2, 3, 4, 5, 10, 7, 8, 9};
     if (!c) return fail(ODO_ERR_ARG, "null ctx");
     if (!c->timing) return fail(ODO_ERR_ARG, "stage timing is off (odo_set_timing)");
@@ -2362,9 +2129,9 @@ struct HypSession {
     DevArena& arena;  // the context's hyp_arena: this session's buffers until the next session
     explicit HypSession(DevArena& a) : arena(a) {}
     DevBuf *xyz = nullptr, *m = nullptr, *g = nullptr, *ints = nullptr, *latch = nullptr, *rng = nullptr,
-           *res = nullptr, *T = nullptr, *scr = nullptr, *bm = nullptr, *phase = nullptr;
+           *res = nullptr, *T = nullptr, *scr = nullptr, *bm = nullptr;
     ~HypSession() {
-        DevBuf* b[] = {xyz, m, g, ints, latch, rng, res, T, scr, bm, phase};
+        DevBuf* b[] = {xyz, m, g, ints, latch, rng, res, T, scr, bm};
         for (DevBuf* x : b) delete x;
     }
 };
@@ -2584,7 +2351,6 @@ static int hyps_launch(odo_ctx* c, const odo_dmatch* m12, int n12, const float* 
     S.T = new DevBuf(A, 16 * sizeof(float));
     S.scr = new DevBuf(A, ransac_scratch_bytes(1, ng, in.words, in.cfg));
     S.bm = new DevBuf(A, (size_t)in.words * 4);
-    S.phase = new DevBuf(A, 2 * sizeof(int));
     ARENA_CHECK(A);
     std::vector<uint64_t> gl(ng);
     for (int k = 0; k < ng; k++) {
@@ -2593,7 +2359,6 @@ static int hyps_launch(odo_ctx* c, const odo_dmatch* m12, int n12, const float* 
         gl[k] = ((uint64_t)(uint32_t)k << 32) | bits;
     }
     const int ints[4] = {ng, ng, 1, 0};
-    const int range[2] = {h0, h1};
     // the inputs packed in page-locked memory in their device order (the
     // arena hands out consecutive 256-B aligned sections, as Pack does): one
     // DMA instead of seven pageable copies. The previous session's upload
@@ -2615,7 +2380,7 @@ static int hyps_launch(odo_ctx* c, const odo_dmatch* m12, int n12, const float* 
             return fail(ODO_ERR_DEVICE, "hipHostMalloc (hypotheses staging) failed");
         c->hyp_stage_cap = cap;
     }
-    if (!c->hyp_up) HIPCHK(hipEventCreateWithFlags(&c->hyp_up, ODO_SYNC_EVENT_FLAGS));
+    if (!c->hyp_up) HIPCHK(hipEventCreateWithFlags(&c->hyp_up, SYNC_EVENT_FLAGS));
     uint8_t* hb = c->hyp_stage_h;
     memcpy(hb + o_xyz, xyz1, (size_t)n1 * 12);
     memcpy(hb + o_xyz + (size_t)kc * 12, xyz2, (size_t)n2 * 12);
@@ -2627,12 +2392,11 @@ static int hyps_launch(odo_ctx* c, const odo_dmatch* m12, int n12, const float* 
     HIPCHK(hipMemcpyAsync(S.xyz->p, hb, up, hipMemcpyHostToDevice, st));
     HIPCHK(hipEventRecord(c->hyp_up, st));
     c->hyp_up_rec = true;
-    // the part-3 launch reads its range from host memory before returning
-    int* hrange = const_cast<int*>(range);
     launch_ransac_raw(st, S.scr->p, 1, ng, in.words, in.cfg, 0, 0, S.rng->as<odo_rng>());
-    launch_ransac(st, S.g->p, S.ints->as<int>(), S.ints->as<int>() + 1, S.m->as<odo_dmatch>(), S.xyz->as<float>(),
-                  kc, 0, ng, in.cfg, S.latch->as<double>(), S.ints->as<int>() + 2, 0, S.rng->as<odo_rng>(), S.scr->p,
-                  S.bm->as<uint32_t>(), in.words, S.res->as<odo_pair_result>(), S.T->as<float>(), 1, 3, hrange);
+    launch_ransac_hyps(st, S.g->p, S.ints->as<int>(), S.ints->as<int>() + 1, S.m->as<odo_dmatch>(),
+                       S.xyz->as<float>(), kc, 0, ng, in.cfg, S.latch->as<double>(), S.ints->as<int>() + 2, 0,
+                       S.rng->as<odo_rng>(), S.scr->p, S.bm->as<uint32_t>(), in.words, S.res->as<odo_pair_result>(),
+                       S.T->as<float>(), 1, h0, h1);
     HIPCHK(hipGetLastError());
     return ODO_OK;
 }

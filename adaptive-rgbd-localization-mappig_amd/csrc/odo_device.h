@@ -615,7 +615,7 @@ ODO_INLINE bool error_function2_shortcut(const float x1[3], const float x2[3], c
 }
 
 // error_function2_mk as straight-line code: every branch becomes a select
-// between the values both sides compute, so the scheduler can interleave two
+// between the values both sides compute, so the compiler can interleave two
 // evaluations (the pivots' square roots, reciprocals and quotients are one
 // long dependency chain; a wave running one evaluation at a time waits on
 // it). Same value as error_function2_mk for every point: each select takes

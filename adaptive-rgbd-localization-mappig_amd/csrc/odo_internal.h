@@ -11,7 +11,7 @@
 
 namespace odo {
 
-// Measurement / A-B knobs (stream schedules, stage skipping, retired kernel
+// Measurement / A-B knobs (serial streams, stage skipping, retired kernel
 // forms, grid sizes). Only the tuning build (make tuning: -DODO_TUNING,
 // build_tuning/libodo_hip.so, selected with ODO_LIB) reads them from the
 // environment; the production library ignores the environment entirely, so a
@@ -266,15 +266,22 @@ void launch_latch(hipStream_t st, double* latch, const void* good, const int* n_
                   const odo_dmatch* matches, const float* xyz, int kp_cap, int slot0, int npairs, int match_cap,
                   int min_inl, int sample_size, int iterations, const int* pair_valid, int* set_flag = nullptr);
 size_t ransac_gpt_bytes();
-// rand() words for every pair (data independent): launched at batch start on
-// a side stream; launch_ransac's stream must wait for it.
+// rand() words for every pair (data independent): launched ahead of
+// launch_ransac on the same stream.
 void launch_ransac_raw(hipStream_t st, void* scratch, int npairs, int match_cap, int mask_words, RansacCfg cfg,
                        uint64_t seed_base, uint64_t pair_base, odo_rng* rng_io);
 void launch_ransac(hipStream_t st, const void* good, const int* n_good, const int* n_matches,
                    const odo_dmatch* matches, const float* xyz, int kp_cap, int slot0, int match_cap, RansacCfg cfg,
                    const double* latch, const int* pair_valid, int min_matches, odo_rng* rng_io, void* scratch,
-                   uint32_t* best_mask, int mask_words, odo_pair_result* res, float* T12, int npairs, int part = 0,
-                   int* phase = nullptr, int* open_hint = nullptr);
+                   uint32_t* best_mask, int mask_words, odo_pair_result* res, float* T12, int npairs,
+                   int* open_hint = nullptr);
+// hypotheses mode: samples of every hypothesis, evaluation of [h_lo, h_hi)
+// only, no fold and no outputs
+void launch_ransac_hyps(hipStream_t st, const void* good, const int* n_good, const int* n_matches,
+                        const odo_dmatch* matches, const float* xyz, int kp_cap, int slot0, int match_cap,
+                        RansacCfg cfg, const double* latch, const int* pair_valid, int min_matches, odo_rng* rng_io,
+                        void* scratch, uint32_t* best_mask, int mask_words, odo_pair_result* res, float* T12,
+                        int npairs, int h_lo, int h_hi);
 size_t ransac_scratch_bytes(int npairs, int match_cap, int mask_words, const RansacCfg& cfg);
 void ransac_read_hyps(hipStream_t st, void* scratch, int match_cap, int mask_words, RansacCfg cfg, int h0, int h1,
                       double* err, int* cnt, float* T);
@@ -292,6 +299,10 @@ void launch_hyp_finish(hipStream_t st, void* scratch, int match_cap, int mask_wo
                        int* payload, int words);
 int hyp_payload_words(int ng);
 size_t pnp_edge_bytes();
+// sel / sel_val (only the pairs with sel[p] == sel_val): no caller passes them
+// any more. Taking them out changed the register allocation of k_pnp<true>
+// (324 -> 330 VGPRs) and measured ~0.3 % slower on the bench line, so the
+// kernel keeps its signature (DESIGN §4 Pipelining).
 void launch_pnp(hipStream_t st, const int32_t* f2_src, const float* xyz, const float* kun, const float* ur,
                 const int* nkp, int kp_cap, int slot0, FrameCalib cal, const float* T12, const int* pair_valid,
                 const int* n_matches, int min_matches, void* edges, odo_pair_result* res, uint8_t* inlier_mask,

@@ -106,7 +106,7 @@ double odo_get_latch(odo_ctx* ctx);
  * results[n] (host): results[i] is the pair (frame i-1 -> frame i); frame -1
  * is the last frame of the previous call. When h_results is NULL the call is
  * asynchronous: the work runs on the library's streams (extraction =
- * odo_stream(), plus pair / PnP / side streams), d_bgr is read by the
+ * odo_stream(), plus two pair streams), d_bgr is read by the
  * extraction stream and d_depth by the batch's pair stream (the keypoint
  * geometry), and odo_synchronize() waits for all of them. */
 int odo_track_batch(odo_ctx* ctx, const uint8_t* d_bgr, const uint16_t* d_depth, int n,

@@ -67,6 +67,18 @@ def test_config_struct_size_checked():
     assert b"struct_size" in lib.odo_last_error()
 
 
+def test_track_entry_points_reject_a_null_context():
+    """Every batch entry point checks its arguments itself, the context
+    included, before touching it (ODO_ERR_ARG = -1; no device call, so this
+    runs on CPU)."""
+    lib = load_pkg().load()
+    buf = (C.c_uint8 * 64)()
+    for name in ("odo_track_batch", "odo_track_batch_async", "odo_track_batch_host", "odo_track_batch_host_async",
+                 "odo_track_batch_host_sparse_depth"):
+        assert getattr(lib, name)(None, buf, buf, 1, buf) == -1, name
+        assert lib.odo_last_error()
+
+
 @pytest.mark.skipif(gpu_available(), reason="checks the no-GPU failure path")
 def test_no_cpu_fallback():
     pkg = load_pkg()

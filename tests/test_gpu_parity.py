@@ -185,6 +185,78 @@ def test_pipelined_batches_roll_and_seeds():
     assert odo.latch == latch
 
 
+def _last_batch_state(odo, n):
+    return ([odo.frame(i) for i in range(n)], [odo.pair(i)["matches"] for i in range(n)], odo.latch)
+
+
+def test_device_pipelined_batches_equal_host_path():
+    """Device inputs, batches queued back to back without a host sync (the
+    roll and the keypoint geometry at the head of the batch's pair stream; six
+    batches over four frame sets, so a set is reused and the extraction's wait
+    for the batch three before it is live): the synchronous call, the async
+    call with streamed records and stage-timing mode 1 (roll and geometry on
+    the extraction stream) all equal the host-input path exactly."""
+    import torch
+    pkg = load_pkg()
+    bgr, dep, _ = sequence(11)
+    cuts = [0, 3, 5, 7, 9, 11]
+    batches = [(a0, min(a0 + 2, b)) for a, b in zip(cuts[:-1], cuts[1:]) for a0 in range(a, b, 2)]
+    assert len(batches) >= 6 and batches[-1] == (9, 11)
+    nl = batches[-1][1] - batches[-1][0]
+
+    # host path: results on the last batch only (pipelined), and on every batch
+    odo, _ = make_odo(pkg, 640, 480, 1000, 300, 3)
+    for a, b in batches[:-1]:
+        odo.track_batch_host(bgr[a:b], dep[a:b], want_results=False)
+    ref_res = odo.track_batch_host(bgr[9:11], dep[9:11])
+    ref_frames, ref_pairs, ref_latch = _last_batch_state(odo, nl)
+    odo.close()
+    odo, _ = make_odo(pkg, 640, 480, 1000, 300, 3)
+    ref_all = [odo.track_batch_host(bgr[a:b], dep[a:b]) for a, b in batches]
+    odo.close()
+    assert np.array_equal(ref_all[-1], ref_res)
+
+    # every batch in its own device tensors, alive until the last synchronize():
+    # the library reads the depth on a pair stream after the call returns
+    dev = [(torch.from_numpy(bgr[a:b]).to("cuda"), torch.from_numpy(dep[a:b].view(np.int16)).to("cuda"))
+           for a, b in batches]
+    torch.cuda.synchronize()
+
+    def check(odo, res, what):
+        frames, pairs, latch = _last_batch_state(odo, nl)
+        assert np.array_equal(res, ref_res), f"{what}: pair records differ from the host path"
+        for i in range(nl):
+            assert np.array_equal(frames[i]["kps"], ref_frames[i]["kps"]), f"{what}: frame {i} keypoints"
+            assert np.array_equal(frames[i]["desc"], ref_frames[i]["desc"]), f"{what}: frame {i} descriptors"
+            assert np.array_equal(pairs[i], ref_pairs[i]), f"{what}: pair {i} match list"
+        assert latch == ref_latch, f"{what}: latch"
+
+    for timing in (False, True):  # runs (a) and (c)
+        odo, _ = make_odo(pkg, 640, 480, 1000, 300, 3)
+        if timing:
+            odo.set_timing(True)
+        for (tb, td), (a, b) in zip(dev[:-1], batches[:-1]):
+            odo.track_batch(tb.data_ptr(), td.data_ptr(), b - a, want_results=False)
+        res = odo.track_batch(dev[-1][0].data_ptr(), dev[-1][1].data_ptr(), nl, want_results=True)
+        if timing:
+            assert len(odo.timings()) == 9
+        check(odo, res, "stage timing" if timing else "sync")
+        odo.close()
+
+    # run (b): records streamed into a pinned ring
+    odo, _ = make_odo(pkg, 640, 480, 1000, 300, 3)
+    ring = pkg.PinnedResults(len(batches), 3)
+    for row, ((tb, td), (a, b)) in enumerate(zip(dev, batches)):
+        odo.track_batch_async(tb.data_ptr(), td.data_ptr(), b - a, ring, row)
+    odo.synchronize()
+    for row, (a, b) in enumerate(batches):
+        assert np.array_equal(ring.all[row][:b - a], ref_all[row]), f"async: records of batch {row}"
+    check(odo, ring.all[len(batches) - 1][:nl].copy(), "async")
+    odo.close()
+    ring.close()
+    del dev
+
+
 @pytest.mark.parametrize("n,levels", [(1, 3), (15, 4), (16, 3), (17, 5), (100, 2), (613, 40), (777, 256),
                                       (2048, 30), (4099, 7), (8192, 200)])
 def test_good_match_sort_is_std_sort(pkg, n, levels):

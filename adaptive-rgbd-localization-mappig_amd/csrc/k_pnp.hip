@@ -635,8 +635,9 @@ ODO_INLINE void edge_build(const SE3M& T, const double Xw[3], const double ob[3]
 // their read-mostly fields (Xw, obs, info, flags: 29 B per edge) are copied
 // into the workgroup's LDS, and every pass of the ~40 Levenberg iterations
 // reads them there instead of from L2 (a pass walks ~2-3 edges per thread,
-// each a dependent L2 round trip before). chi4 and idx stay in HBM. The host
-// picks LE when kp_cap edges fit (pnp_lds_bytes).
+// each a dependent L2 round trip before). The passes' chi2 per trial slot is
+// kept there too, as float (16 B per edge; 45 B in all); idx stays in HBM.
+// The host picks LE when kp_cap edges fit (pnp_lds_bytes).
 template <bool LE>
 __global__ void __launch_bounds__(PNP_NT, PNP_WAVES_PER_EU) k_pnp(const int32_t* __restrict__ f2_src, const float* __restrict__ xyz,
                                             const float* __restrict__ kun, const float* __restrict__ ur,
@@ -1076,8 +1077,12 @@ __global__ void __launch_bounds__(PNP_NT, PNP_WAVES_PER_EU) k_pnp(const int32_t*
 
 namespace odo {
 size_t pnp_edge_bytes() { return PE_BYTES; }
-// dynamic LDS of k_pnp<true>: 29 B per edge slot (kp_cap), 0 = edges stay in
-// HBM (k_pnp<false>). ODO_PNP_LDS (tuning builds) = 0 disables it for A/B.
+// dynamic LDS of k_pnp<true>: 45 B per edge slot (kp_cap): Xw and obs 12 B
+// each, info 4 B, flags 1 B, and the four trial slots' float chi2, 16 B. The
+// chi2 floats follow the kp_cap flag bytes, so kp_cap must be a multiple of 4
+// for their alignment (callers pass a multiple of 64). 0 = edges stay in HBM
+// (k_pnp<false>): with PNP_LDS_MAX = 96 KiB, kp_cap up to 2176 takes the LDS
+// form. ODO_PNP_LDS (tuning builds) = 0 disables it for A/B.
 #ifndef PNP_LDS_MAX
 #define PNP_LDS_MAX (96 * 1024)
 #endif
@@ -1138,8 +1143,9 @@ ODO_INLINE void block_reduce(double (&v)[NV], double* red /* 4*NV */) {
 // ============================================================ Kabsch::Compute
 // Odometry/kabsch.cpp:14-57 (dead code in the reference, exported for
 // completeness): centroids, A = (A-cA)^T (B-cB), JacobiSVD (same 3x3 Jacobi as
-// the RANSAC fit), R = W diag(1,1,sgn det A) V^T, t = -R cA + cB. One
-// workgroup; sums use the fixed-order block reduction.
+// the RANSAC fit), R = W diag(1,1,sg) V^T with sg = sgn(det V det W) (= sgn
+// det A for a full-rank A; a rotation for rank-deficient input too),
+// t = -R cA + cB. One workgroup; sums use the fixed-order block reduction.
 namespace odo {
 __global__ void __launch_bounds__(PNP_THREADS) k_kabsch(const float* __restrict__ A, const float* __restrict__ B, int n,
                                                         float* __restrict__ T) {
@@ -1170,8 +1176,17 @@ __global__ void __launch_bounds__(PNP_THREADS) k_kabsch(const float* __restrict_
         float M[3][3], Vm[3][3], S[3], Wm[3][3];
         for (int i = 0; i < 9; i++) M[i / 3][i % 3] = (float)m[i];
         svd3(M, Vm, S, Wm);  // V = svd.matrixU(), W = svd.matrixV()
-        const float d = det3(M);
-        const float sg = (d != 0.f) ? (float)((d > 0.f) - (d < 0.f)) : 1.f;
+        // kabsch.cpp takes sgn det M (0 -> +1). det M = det V * s0 s1 s2 * det W,
+        // so for a full-rank M that is sgn(det V det W), which is what we
+        // take: for a rank-deficient M (coplanar, collinear or identical
+        // points, n < 4) det M is 0 or rounding noise while the SVD's bases
+        // may still differ in handedness, and the reference's rule can then
+        // return a reflection. With the bases' own sign det R = det W * sg *
+        // det V = +1 for every input: coplanar points get the one rotation
+        // their data fix; for collinear or identical points R is a rotation
+        // whose part about the line (all of it for identical points) is
+        // whatever rounding left in M, as nothing in the data fixes it
+        const float sg = (det3(Vm) * det3(Wm) < 0.f) ? -1.f : 1.f;
         float R[3][3];
         for (int i = 0; i < 3; i++)
             for (int j = 0; j < 3; j++) R[i][j] = Wm[i][0] * Vm[j][0] + Wm[i][1] * Vm[j][1] + Wm[i][2] * sg * Vm[j][2];

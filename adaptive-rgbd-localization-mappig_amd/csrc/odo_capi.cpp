@@ -2605,7 +2605,10 @@ int odo_pnp_motion_ba(odo_ctx* c, const float* Xw, const float* obs, int n, cons
                       const float Tcw_init[16], float Tcw_out[16], uint8_t* outlier, int* n_inliers) {
     if (!c || n < 0 || (n && (!Xw || !obs)) || !Tcw_init || !Tcw_out || !n_inliers) return fail(ODO_ERR_ARG, "bad pnp args");
     hipStream_t st = c->stream;
-    const int kc = std::max(n, 1);
+    // the edge capacity, a multiple of 64 as k_pnp<true>'s LDS carve-up
+    // requires (its float chi2 slots follow kp_cap flag bytes)
+    if (n > (1 << 30)) return fail(ODO_ERR_CAPACITY, "pnp: too many edges");
+    const int kc = (std::max(n, 1) + 63) & ~63;
     DevArena& A = c->arena;
     A.begin();
     // inputs packed into the pinned staging buffer, one upload; the result

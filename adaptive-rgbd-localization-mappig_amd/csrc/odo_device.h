@@ -268,10 +268,18 @@ struct TFC {
         const float oma = 1.0f - alpha;
         if (FD) {
             // guarded launch (finite coordinates): a point the lane does not
-            // add updates with alpha = 0, 1 - alpha = 1, which leaves every
-            // accumulator's bits as they are — x + (+-0) = x, as none of them
-            // is ever -0 (they start at +0, and a sum is -0 only when both
-            // terms are) — so 2 selects replace the 15 below
+            // add updates with alpha = 0, 1 - alpha = 1, so 2 selects replace
+            // the 15 below. m1 and m2 keep their bits: x + (+-0) = x unless
+            // x is -0, and they never are (they start at +0, and a sum is -0
+            // only when both terms are). cov can be -0: the first member has
+            // alpha = 1, so cov = 0 * (0 + d2 * d1) is -0 wherever the
+            // product is negative, and a non-member after it turns that into
+            // -0 + (+0) = +0. The transform does not see the sign: the next
+            // member whose term ad2 * d1 is nonzero absorbs either zero into
+            // the same sum, and where every later term is zero too (a
+            // coordinate all members share) the entry stays a zero, of which
+            // svd3 reads only fabsf and a < 0. tests/test_pose_solvers_gpu.py
+            // compares T12 by bit pattern on such geometry
             const float al = u ? alpha : 0.0f, om = u ? oma : 1.0f;
 #pragma unroll
             for (int i = 0; i < 3; i++) {

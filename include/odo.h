@@ -341,7 +341,11 @@ int odo_projection_match(odo_ctx* ctx, const float Tcw[16], const odo_landmark* 
                          int* n_matches);
 
 /* Kabsch::Compute (kabsch.cpp:14): one GPU workgroup (k_kabsch: centroids, A^T B
- * with a fixed-order block reduction, 3x3 Jacobi SVD). A,B: n x 3 host arrays. */
+ * with a fixed-order block reduction, 3x3 Jacobi SVD). A,B: n x 3 host arrays.
+ * R = W diag(1, 1, sgn(det V det W)) V^T is a rotation for every input (the
+ * reference's sgn det M can give a reflection for rank-deficient sets); for
+ * collinear or identical points its turn about the line is not determined by
+ * the data. n = 0 returns the identity. */
 int odo_kabsch(const float* A, const float* B, int n, float T[16]);
 
 /* glibc rand() stream helpers (srand/rand of main.cpp:27, ransac.cpp:275). */

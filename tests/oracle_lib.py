@@ -220,6 +220,63 @@ def check_ransac_inliers(gpu_pair, ref, tag):
                                       f"{np.nonzero(got != exp)[0][:8]}")
 
 
+def assert_same_bits(got, ref, what, dtype=np.float32):
+    """got == ref by bit pattern (.view of the unsigned integer of the same
+    width): unlike np.array_equal, -0.0 differs from +0.0, and a NaN equals
+    the same NaN. Scalars and ctypes arrays are taken as `dtype`."""
+    g = np.ascontiguousarray(np.asarray(got, dtype)).ravel()
+    r = np.ascontiguousarray(np.asarray(ref, dtype)).ravel()
+    u = {4: np.uint32, 8: np.uint64}[np.dtype(dtype).itemsize]
+    assert g.shape == r.shape, f"{what}: {g.size} values vs {r.size}"
+    gb, rb = g.view(u), r.view(u)
+    if not np.array_equal(gb, rb):
+        bad = np.nonzero(gb != rb)[0]
+        raise AssertionError(f"{what}: bit patterns differ at {bad[:8]}: {g[bad[:8]]!r} "
+                             f"({[hex(int(x)) for x in gb[bad[:8]]]}) vs {r[bad[:8]]!r} "
+                             f"({[hex(int(x)) for x in rb[bad[:8]]]})")
+
+
+def assert_ransac_bits(got, ref, tag):
+    """One RANSAC result against another by bit pattern. got / ref: dicts with
+    T12 (16 floats), rmse, ok, inliers (DMATCH_DTYPE array), and optionally
+    latch (double) and rng (a Rng-like structure with state, fpos, rpos)."""
+    assert int(got["ok"]) == int(ref["ok"]), f"{tag}: ok {got['ok']} vs {ref['ok']}"
+    assert_same_bits(got["T12"], ref["T12"], f"{tag}: T12")
+    assert_same_bits(got["rmse"], ref["rmse"], f"{tag}: rmse")
+    gi, ri = np.asarray(got["inliers"]), np.asarray(ref["inliers"])
+    assert len(gi) == len(ri), f"{tag}: {len(gi)} inliers vs {len(ri)}"
+    assert gi.tobytes() == ri.tobytes(), f"{tag}: inlier list differs"
+    if "latch" in ref:
+        assert_same_bits(got["latch"], ref["latch"], f"{tag}: latch", np.float64)
+    if "rng" in ref:
+        a, b = got["rng"], ref["rng"]
+        assert list(a.state) == list(b.state) and (a.fpos, a.rpos) == (b.fpos, b.rpos), f"{tag}: rand() state"
+
+
+def ransac_pair(lib_ransac, is_oracle, m, xyz1, xyz2, rp, rng, latch):
+    """Ransac::Iterate through oracle_ransac (is_oracle) or odo_ransac
+    (lib_ransac = functools.partial(lib.odo_ransac, ctx)); rng and latch (a
+    c_double) are updated in place. Returns the dict assert_ransac_bits takes,
+    plus visited / n_good from the oracle."""
+    nm = len(m)
+    T = np.zeros(16, np.float32)
+    rmse = C.c_float(0)
+    inl = np.zeros(max(nm, 1), DMATCH_DTYPE)
+    ni, a, b = C.c_int(0), C.c_int(0), C.c_int(0)
+    out = {}
+    if is_oracle:
+        ok = lib_ransac(ptr(m), nm, ptr(xyz1), ptr(xyz2), C.byref(rp), C.byref(rng), C.byref(latch), ptr(T),
+                        C.byref(rmse), ptr(inl), C.byref(ni), C.byref(a), C.byref(b))
+        out.update(visited=a.value, n_good=b.value)
+    else:
+        rc = lib_ransac(ptr(m), nm, ptr(xyz1), len(xyz1), ptr(xyz2), len(xyz2), C.byref(rp), C.byref(rng),
+                        C.byref(latch), ptr(T), C.byref(rmse), ptr(inl), C.byref(ni), C.byref(a))
+        assert rc == 0, f"odo_ransac returned {rc}"
+        ok = a.value
+    out.update(T12=T, rmse=rmse.value, ok=ok, inliers=inl[:ni.value], latch=latch.value, rng=rng)
+    return out
+
+
 def adaptive_params() -> AdaptiveParams:
     p = AdaptiveParams()
     lib().oracle_adaptive_default(C.byref(p))

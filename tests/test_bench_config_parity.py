@@ -170,6 +170,8 @@ def _compare(name, c, odo, res, oracle, full=True, pnp=True):
             f"{tag}: RANSAC work counts (sweeps, fit points)"
         assert np.array_equal(res[p]["T12"], np.array(r.T12, np.float32)), f"{tag}: T12"
         assert res[p]["rmse"] == np.float32(r.rmse), f"{tag}: rmse"
+        O.assert_same_bits(res[p]["T12"], r.T12, f"{tag}: T12")  # a zero's sign included
+        O.assert_same_bits(res[p]["rmse"], r.rmse, f"{tag}: rmse")
         O.check_ransac_inliers(g, r, tag)
         if not pnp:
             continue

@@ -375,6 +375,8 @@ def test_ransac_entry_point_stream_and_latch(pkg, iters, corrupt):
         print(f"iters {iters} corrupt {corrupt}: good {ng.value} visited {vis.value} inliers {ni_ref.value}")
         assert ok.value == ok_ref and ni.value == ni_ref.value
         assert np.array_equal(T, T_ref) and rmse.value == rmse_ref.value
+        O.assert_same_bits(T, T_ref, "T12")  # a zero's sign included
+        O.assert_same_bits(rmse.value, rmse_ref.value, "rmse")
         assert np.array_equal(inl[:ni.value], inl_ref[:ni_ref.value])
         assert lat_gpu.value == lat_ref.value
         assert list(r_gpu.state) == list(r_ref.state) and (r_gpu.fpos, r_gpu.rpos) == (r_ref.fpos, r_ref.rpos)

@@ -189,10 +189,6 @@ __global__ void __launch_bounds__(256) k_oa_scand(const uint8_t* __restrict__ cp
         reinterpret_cast<uint32_t*>(s)[r * nq + q] = smap4(W);
     }
     __syncthreads();
-#ifdef OA_SCAND_NO_NMS  // measurement only (wrong results): the S part alone
-    if (threadIdx.x == 0) band_cnt[(size_t)f * nbands + blockIdx.x] = s[threadIdx.x] & 0;
-    return;
-#endif
     // NMS four pixels at a time: item (r, k) = the S dword of band row r at
     // columns OA_X0 + 4k .. +3. The 3x3 neighbourhood max of its four bytes
     // comes from byte-shifted dwords (v_alignbyte) split into (b0, b2) / (b1,

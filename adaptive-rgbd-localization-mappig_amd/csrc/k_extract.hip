@@ -7,7 +7,7 @@
 //   k_fast_seg    FAST-9/16 + NMS per 30px cell       orbextractor.cpp:669-723
 //   k_octree      DistributeOctTree                   orbextractor.cpp:466-663
 //   k_blur        GaussianBlur 7x7 s=2 REFLECT_101    orbextractor.cpp:795-796
-//   k_finalize    (k_finalize.hip) IC_Angle + rBRIEF + scale; k_kp_geometry undistort + depth
+//   k_finalize_lds (k_finalize.hip) IC_Angle + rBRIEF + scale; k_kp_geometry undistort + depth
 //                 orbextractor.cpp:14-85,805-811; frame.cpp:139-164,286-313
 #include "odo_device.h"
 #include "odo_internal.h"
@@ -164,9 +164,6 @@ constexpr int kCircleDy[16] = {3, 3, 2, 1, 0, -1, -2, -3, -3, -3, -2, -1, 0, 1, 
 #define FS_TH 256
 #define FS_RING 512  // survivors per wave ring (u16 offsets): <= 127 pending + 256 per compass step
 #define FS_RSTRIDE (FS_RING + 8)  // a wave's ring + its trash slot (entry FS_RING), 16-byte multiple
-#ifndef FS_APPEND
-#define FS_APPEND 1  // the ring append by per-pixel ballots (1) or a DPP prefix sum (0)
-#endif
 #define FS_CL 1024   // corner list (a level-0 segment of 7 cells: ~270); beyond it NMS and placement scan the score map
 
 ODO_INLINE void wave_lds_sync() {
@@ -373,16 +370,14 @@ __global__ void __launch_bounds__(FS_TH) k_fast_seg(const uint8_t* __restrict__ 
                     // pixel i's sign bit (bit 15 / 31 of half i / 2) to bit 8i + 7
                     pass4 = __builtin_amdgcn_perm(hm[1], hm[0], 0x07050301u) & e.x;
                 }
-#if FS_APPEND
                 // append to the ring (any order): pixel 0 of every lane's quad
                 // in lane order, then pixel 1, ...: a pixel's slot is the tail
                 // plus the survivors before it in that order (one ballot per
                 // pixel, mbcnt with the running tail as its addend). Every lane
                 // writes four entries, a pixel that did not survive to the
-                // wave's trash slot (no divergent branches). Until round 6:
-                // a DPP prefix sum of the lanes' counts and per-lane popcounts
-                // (the select takes the ballot itself as its lane mask: bit l
-                // of the ballot is lane l's condition)
+                // wave's trash slot (no divergent branches; the select takes the
+                // ballot itself as its lane mask: bit l of the ballot is lane
+                // l's condition)
                 uint32_t pos = (uint32_t)tail;
 #pragma unroll
                 for (int k = 0; k < 4; k++) {
@@ -397,22 +392,6 @@ __global__ void __launch_bounds__(FS_TH) k_fast_seg(const uint8_t* __restrict__ 
                     pos += (uint32_t)__popcll(bk);
                 }
                 tail = (int)pos;
-#else
-                // append to the ring (any order): this lane's survivors after
-                // those of the lanes below (a DPP prefix sum of the counts)
-                const int c = __builtin_popcount(pass4);
-                const int incl = wave_incl_scan(c);
-                const int pos = tail + incl - c;
-                // every lane writes four entries: pixel k of the quad to its
-                // ring slot if it survived, else to the wave's trash slot (no
-                // divergent branches)
-#pragma unroll
-                for (int k = 0; k < 4; k++) {
-                    const int slot = (pos + __builtin_popcount(pass4 & ((1u << (8 * k)) - 1u))) & (FS_RING - 1);
-                    ring[(pass4 >> (8 * k + 7)) & 1u ? slot : FS_RING] = (uint16_t)(qoff + k);
-                }
-                tail += __builtin_amdgcn_readlane(incl, 63);
-#endif
                 if (tail - head >= 128) {
                     wave_lds_sync();
                     do {
@@ -651,9 +630,6 @@ __global__ void __launch_bounds__(OT_THREADS) k_octree(const uint32_t* __restric
                                                        uint32_t* __restrict__ okp, int* __restrict__ ocnt, int okp_stride,
                                                        int node_cap) {
     EXTRACT_PRIO();
-#ifdef ODO_OCTREE_PRIO
-    __builtin_amdgcn_s_setprio(ODO_OCTREE_PRIO);  // tuning: the barrier-bound octree's waves ahead of co-runners
-#endif
     extern __shared__ __attribute__((aligned(16))) char smem[];
     // grid (levels, frames). Measured and retired: (frames, levels), every
     // frame's level 0 (the longest workgroups) dispatched first: 129 vs
@@ -1306,16 +1282,6 @@ __global__ void __launch_bounds__(256) k_blur(const uint8_t* __restrict__ pyr, u
 // two v_perm per dword from per-lane selectors. Widths that are not a
 // multiple of 4 leave garbage in the row padding past w, never read.
 #define BR_R 30  // output rows per chunk (a multiple of 6; levels are >= 40 rows)
-#ifndef BW_ROLL
-#define BW_ROLL 1  // blur walk rows loaded as a rolling 6-row queue (see blur_walk)
-#endif
-#ifndef PYR_NT
-// nontemporal (streaming) accesses for the pyramid's data that is not read
-// again soon: bit 0 the BGR loads, bit 1 the blurred-level stores (finalize
-// reads them a millisecond later), so they do not evict from L2 the levels the
-// next resize and blur walks read back
-#define PYR_NT 0
-#endif
 struct BlurRows {
     int base[17];   // first strip item of each level (prefix); base[nlevels] = items
     int nst[16];    // strips of 16 quads across the interior
@@ -1354,9 +1320,6 @@ ODO_INLINE void blur_walk(const uint8_t* s0, uint8_t* dp, size_t pitch, int h, i
     static_assert(R % 6 == 0, "the accumulators rotate over 6 rows");
     constexpr int NB = (R + 6) / 6;
     uint32_t cw[6][3];
-#if !BW_ROLL
-    uint32_t nw[6][3];
-#endif
     const uint8_t* sp = s0 + (size_t)(y0 - 3) * pitch;
     // input row 6b + j of the walk (rows y0 - 3 ...) into d
     auto load_row = [&](uint32_t(&d)[3], int b, int j, bool refl) {
@@ -1378,21 +1341,15 @@ ODO_INLINE void blur_walk(const uint8_t* s0, uint8_t* dp, size_t pitch, int h, i
     };
     load_block(cw, 0, top);
     for (int b = 0; b < NB; b++) {
-#if !BW_ROLL
-        if (b + 1 < NB) load_block(nw, b + 1, b + 1 == NB - 1 && bottom);
-#else
-        // BW_ROLL: a 6-row queue instead of two 6-row blocks: row j of block b
+        // a rolling 6-row queue instead of two 6-row blocks: row j of block b
         // + 1 is loaded into row j's registers as soon as row j of block b has
         // been consumed (6 rows in flight, 18 registers fewer)
         const bool nref = b + 1 == NB - 1 && bottom;
-#endif
 #pragma unroll
         for (int j = 0; j < 6; j++) {
             // input row r = y0 - 3 + 6b + j
             uint32_t w0 = cw[j][0], w1 = cw[j][1], w2 = cw[j][2];
-#if BW_ROLL
             if (b + 1 < NB) load_row(cw[j], b + 1, j, nref);
-#endif
             if (EDGE) {
                 // the row's bytes x-4 .. x+7 with reflected columns
                 const uint32_t e0 = __builtin_amdgcn_perm(w1, w0, selA[0]) | __builtin_amdgcn_perm(w2, w2, selB[0]);
@@ -1433,19 +1390,11 @@ ODO_INLINE void blur_walk(const uint8_t* s0, uint8_t* dp, size_t pitch, int h, i
             if (b > 0 && store) {
                 const uint32_t lo = __builtin_amdgcn_perm(s1v, s0v, 0x0c0c0602u);
                 const uint32_t hi = __builtin_amdgcn_perm(s3v, s2v, 0x06020c0cu);
-                if (PYR_NT & 2)
-                    __builtin_nontemporal_store(lo | hi, reinterpret_cast<uint32_t*>(dp));
-                else
-                    *reinterpret_cast<uint32_t*>(dp) = lo | hi;
+                *reinterpret_cast<uint32_t*>(dp) = lo | hi;
                 dp += pitch;
             }
         }
-#if BW_ROLL
         sp += 6 * pitch;
-#else
-#pragma unroll
-        for (int j = 0; j < 6; j++) cw[j][0] = nw[j][0], cw[j][1] = nw[j][1], cw[j][2] = nw[j][2];
-#endif
     }
 }
 
@@ -1547,9 +1496,10 @@ __global__ void __launch_bounds__(256) k_blur_rows(const uint8_t* __restrict__ p
 // so no separate blur launch follows (uint8 blur pyramid written to `blur`).
 #ifndef PYR_TH
 // threads per frame workgroup. 512 (round 6): 2 waves per SIMD at <= 80
-// VGPRs (BW_ROLL) = 160 registers, so a frame's workgroup fits on a CU that
-// holds a k_pnp workgroup (328 per SIMD); at 1024 (352) it waited for PnP
-// to drain off the CU on every other step (DESIGN §4 Pipelining)
+// VGPRs (the blur walk's rolling row queue) = 160 registers, so a frame's
+// workgroup fits on a CU that holds a k_pnp workgroup (328 per SIMD); at 1024
+// (352) it waited for PnP to drain off the CU on every other step (DESIGN §4
+// Pipelining)
 #define PYR_TH 512
 #endif
 #ifndef PYR_VGPR
@@ -1680,13 +1630,7 @@ ODO_INLINE void pyr_gray_rows(const uint8_t* __restrict__ src, uint8_t* gdst, in
                 const int q = q0 + u * PYR_TH;
                 if (q < nq4) {
                     const uint32_t* s32 = reinterpret_cast<const uint32_t*>(src + (size_t)q * 12);
-                    if (PYR_NT & 1) {
-                        wv[u][0] = __builtin_nontemporal_load(s32);
-                        wv[u][1] = __builtin_nontemporal_load(s32 + 1);
-                        wv[u][2] = __builtin_nontemporal_load(s32 + 2);
-                    } else {
-                        wv[u][0] = s32[0], wv[u][1] = s32[1], wv[u][2] = s32[2];
-                    }
+                    wv[u][0] = s32[0], wv[u][1] = s32[1], wv[u][2] = s32[2];
                 }
             }
 #pragma unroll

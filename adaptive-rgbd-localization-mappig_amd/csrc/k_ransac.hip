@@ -40,9 +40,6 @@ struct GoodPt {
 };
 
 #define EV_WAVES_C 4   // waves per k_ransac_eval workgroup (EV_WAVES below)
-#ifndef EV2_FOLD_WAVE
-#define EV2_FOLD_WAVE 1  // the second launch's ordered fold by the whole wave (0: lane 0)
-#endif
 #ifndef EV_H0
 // hypotheses per pair in the first eval launch of a batch (round 5: 2; a row
 // of 4 until round 4). In the bench's sequence 52 of 64 pairs break at
@@ -557,7 +554,7 @@ __global__ void __launch_bounds__(256) k_ransac_prep(RansacBufs B, RansacCfg cfg
     }
     __syncthreads();
     if (t == 0) {
-        S->efast = active && EF_FAST == 2 && s_efast_ok;
+        S->efast = active && s_efast_ok;
         S->active = active ? 1 : 0;
         S->ng = ng;
         S->S = Ssz;
@@ -743,21 +740,12 @@ ODO_INLINE double fold_dv(const EvalLds& L, int nin, double s) {
     return s;
 }
 
-
-// The pair's good-match table is staged in LDS (shared by the workgroup's
-// waves) when it fits; every refinement sweeps it twice.
-#ifndef PCACHE
-#define PCACHE 0
-#endif
-// dynamic LDS of k_ransac_eval: good-point cache + one TFC slab per wave
-#define EV_LDS (PCACHE * sizeof(GoodPt) + (size_t)EV_WAVES * 8 * TFC_CAP * sizeof(float))
+// dynamic LDS of k_ransac_eval: one TFC slab per wave
+#define EV_LDS ((size_t)EV_WAVES * 8 * TFC_CAP * sizeof(float))
 extern __shared__ __align__(16) uint8_t ev_dyn[];
-
-template <bool CACHED>
-ODO_INLINE GoodPt load_pt(const GoodPt* P, int k) {
-    if (CACHED) return reinterpret_cast<const GoodPt*>(ev_dyn)[k];
-    return P[k];
-}
+// a good point by value (spelling the loads out at the call sites changes the
+// compiled kernels)
+ODO_INLINE GoodPt load_pt(const GoodPt* P, int k) { return P[k]; }
 
 #ifdef ODO_RANSAC_PROFILE
 #define RPROF_MAX 4096
@@ -951,19 +939,12 @@ ODO_INLINE void try_fold_wave(const RansacBufs& B, const RansacCfg& cfg, int p, 
     }
 }
 
-#ifndef EV_EFAST
-#define EV_EFAST 1  // the evaluation kernels take the fast ErrorFunction2 form for guarded pairs
-#endif
-#ifndef EV_Z
-#define EV_Z 1  // ... and the per-hypothesis covariance products (hyp_cov_terms)
-#endif
-template <bool CACHED>
 ODO_INLINE void eval_hyps(const RansacBufs& B, const RansacCfg& cfg, int p, int wave, int lane, EvalLds& L,
                           const GoodPt* P, int ng, int words, int H, int hofs, int y0, int hlim, int yrow,
                           int ystride) {
     RState* S = B.st + p;
     const int* smp0 = B.samples + (size_t)p * B.hcap * SREC;
-    const TfcSlab TS{reinterpret_cast<float*>(ev_dyn + PCACHE * sizeof(GoodPt)) + (size_t)wave * 8 * TFC_CAP};
+    const TfcSlab TS{reinterpret_cast<float*>(ev_dyn) + (size_t)wave * 8 * TFC_CAP};
     MahalConst K;
     K.raster_cov_x = cfg.raster_cov_x;
     K.raster_cov_y = cfg.raster_cov_y;
@@ -972,7 +953,7 @@ ODO_INLINE void eval_hyps(const RansacBufs& B, const RansacCfg& cfg, int p, int 
     const unsigned minInl = (unsigned)cfg.min_inlier_th;
     // the pair's points passed k_ransac_prep's range guard (RState.efast):
     // ErrorFunction2's fast form, the same bits (odo_device.h); wave-uniform
-    const bool efast = EV_EFAST && EF_FAST == 2 && __builtin_amdgcn_readfirstlane(S->efast) && ef_fast_cov(K);
+    const bool efast = __builtin_amdgcn_readfirstlane(S->efast) && ef_fast_cov(K);
     // this launch's waves stride over hypotheses [hofs + y0*EV_WAVES, hlim)
     const int hend = min(H, hlim);
     for (int h = hofs + (y0 + yrow) * EV_WAVES + wave; h < hend; h += ystride * EV_WAVES) {
@@ -1006,7 +987,7 @@ ODO_INLINE void eval_hyps(const RansacBufs& B, const RansacCfg& cfg, int p, int 
                 bool in = false;
                 GoodPt g;
                 if (lane < ns) {
-                    g = load_pt<CACHED>(P, smp[1 + lane]);
+                    g = load_pt(P, smp[1 + lane]);
                     in = tfc_point_ok(g);
                 }
                 const uint64_t bal = __ballot(in);
@@ -1023,7 +1004,7 @@ ODO_INLINE void eval_hyps(const RansacBufs& B, const RansacCfg& cfg, int p, int 
                     bool in = false;
                     GoodPt g;
                     if (k < ng && ((L.cur[k >> 5] >> (k & 31)) & 1)) {
-                        g = load_pt<CACHED>(P, k);
+                        g = load_pt(P, k);
                         in = tfc_point_ok(g);
                     }
                     const uint64_t bal = __ballot(in);
@@ -1057,7 +1038,7 @@ ODO_INLINE void eval_hyps(const RansacBufs& B, const RansacCfg& cfg, int p, int 
 #pragma unroll
             for (int i = 0; i < 12; i++) Td[i] = (double)T[i];
             double Zd[6];  // the covariance's point-independent products, once per sweep
-            if (EV_Z) hyp_cov_terms(Td, K, Zd);
+            hyp_cov_terms(Td, K, Zd);
             RP_ACC(t_get);
             RP_T0();
             // poll the fold's stop flag once per refinement: issued here, read
@@ -1072,10 +1053,10 @@ ODO_INLINE void eval_hyps(const RansacBufs& B, const RansacCfg& cfg, int p, int 
                 bool in = false;
                 double d = 0.0;
                 if (k < ng) {
-                    const GoodPt g = load_pt<CACHED>(P, k);
+                    const GoodPt g = load_pt(P, k);
                     if (!(g.sz == 0.0f || g.tx == 0.0f)) {
                         const float x1[3] = {g.sx, g.sy, g.sz}, x2[3] = {g.tx, g.ty, g.tz};
-                        d = error_function2_mk(x1, x2, Td, K, EV_Z ? Zd : nullptr, efast);
+                        d = error_function2_mk(x1, x2, Td, K, Zd, efast);
                         in = !(d > th) && (d >= 0.0);
                     }
                 }
@@ -1175,6 +1156,7 @@ ODO_INLINE void eval_hyps(const RansacBufs& B, const RansacCfg& cfg, int p, int 
 #ifndef EV_MIN_BLOCKS
 #define EV_MIN_BLOCKS 2
 #endif
+// hofs is 0 in every launch (k_ransac_eval_list takes the hypotheses past h0); the signature stays as compiled
 __global__ void __launch_bounds__(64 * EV_WAVES, EV_MIN_BLOCKS) k_ransac_eval(RansacBufs B, RansacCfg cfg, int hofs, int y0,
                                                                                   int hlim) {
     __builtin_amdgcn_s_setprio(ODO_WAVE_PRIO);  // latency-bound: issue ahead of co-resident extraction waves
@@ -1190,14 +1172,7 @@ __global__ void __launch_bounds__(64 * EV_WAVES, EV_MIN_BLOCKS) k_ransac_eval(Ra
     if (s_done) return;  // uniform over the workgroup
     const int ng = S->ng, words = S->words;
     const GoodPt* P = B.gpts + (size_t)p * B.match_cap;
-    if (PCACHE > 0 && ng <= PCACHE) {
-        GoodPt* pc = reinterpret_cast<GoodPt*>(ev_dyn);
-        for (int k = threadIdx.x; k < ng; k += blockDim.x) pc[k] = P[k];
-        __syncthreads();
-        eval_hyps<true>(B, cfg, p, wave, lane, s_w[wave], P, ng, words, H, hofs, y0, hlim, blockIdx.y, gridDim.y);
-    } else {
-        eval_hyps<false>(B, cfg, p, wave, lane, s_w[wave], P, ng, words, H, hofs, y0, hlim, blockIdx.y, gridDim.y);
-    }
+    eval_hyps(B, cfg, p, wave, lane, s_w[wave], P, ng, words, H, hofs, y0, hlim, blockIdx.y, gridDim.y);
 }
 
 // The pairs still folding after the first launch, in pair order, and a work
@@ -1255,8 +1230,7 @@ __global__ void __launch_bounds__(64 * EV_WAVES, EV_MIN_BLOCKS) k_ransac_eval_li
         const int H = S->H;
         if (hofs + row * EV_WAVES >= H || ld_relaxed(&S->done)) continue;  // uniform per item
         const GoodPt* P = B.gpts + (size_t)p * B.match_cap;
-        eval_hyps<false>(B, cfg, p, wave, lane, s_w[wave], P, S->ng, S->words, H, hofs, row,
-                         hofs + (row + 1) * EV_WAVES, 0, 1);
+        eval_hyps(B, cfg, p, wave, lane, s_w[wave], P, S->ng, S->words, H, hofs, row, hofs + (row + 1) * EV_WAVES, 0, 1);
     }
 }
 
@@ -1284,30 +1258,18 @@ ODO_INLINE double readlane_d(double v, int l) {
 }
 #define LN_WAVES 4
 #define LN_RS 33  // LDS row stride (doubles) of the parked terms
-#ifndef LN_TFAST
-#define LN_TFAST 1  // the fast-form launch also takes the TFC division's fast form (tfc_div)
-#endif
-#ifndef LN_TD
-// 1: the active slots' transforms parked in LDS as doubles, with their
+// The active slots' transforms are parked in LDS as doubles, with their
 // point-independent covariance terms (hyp_cov_terms), so the sweep's
 // evaluations read them instead of converting twelve floats and forming six
 // products each time (the same values: the conversions are exact and Z's
 // products are the ones error_function2_mk forms without it)
-#define LN_TD 1
-#endif
-// LDS words per slot: 12 + 6 doubles (1), 12 doubles without the covariance
-// terms (2), or 12 floats (0)
-#define LN_TW (LN_TD == 1 ? 18 : 12)
+#define LN_TW 18  // LDS doubles per slot: 12 + 6
 #ifndef LN_SLOTS
 #define LN_SLOTS 32  // lanes per wave that take up hypotheses (rows of parked terms per wave)
 #endif
 #ifndef LN_PRIO
 #define LN_PRIO ODO_WAVE_PRIO  // k_ransac_lanes' wave priority
 #endif
-#ifndef LN_BAL_EXP
-#define LN_BAL_EXP 1  // LN_BAL weight: (good matches + 1) ^ LN_BAL_EXP (1 or 2)
-#endif
-ODO_INLINE int ln_weight(int ng) { return LN_BAL_EXP == 2 ? ((ng + 1) * (ng + 1) + 63) >> 6 : ng + 1; }
 #ifdef ODO_LANES_PROFILE
 // -DODO_LANES_PROFILE: per wave of the last k_ransac_lanes launch: start, end,
 // loop rounds, sum of active lanes over the rounds, TFC / sweep ticks and the
@@ -1327,7 +1289,6 @@ static_assert(LN_SLOTS <= 64, "a wave's hypothesis slots are its lanes");
 template <bool EFAST>
 ODO_INLINE void lanes_body(const RansacBufs& B, const RansacCfg& cfg, uint32_t* lane_slab, int waves_total,
                            int min_open, int lane, int wv, int gw, GoodPt* lp, double* lres, int* la, double* lTd) {
-    float* const lT = reinterpret_cast<float*>(lTd);
     const int cnt = B.open_cnt[0];
     if (cnt < min_open || cnt <= 0) return;  // few open pairs: latency matters, k_ransac_eval_list takes them
     uint32_t* slab = lane_slab + (size_t)gw * 2 * B.mask_words * 64;
@@ -1357,14 +1318,14 @@ ODO_INLINE void lanes_body(const RansacBufs& B, const RansacCfg& cfg, uint32_t* 
         int tot = 0;
         for (int i0 = 0; i0 < cnt; i0 += 64) {
             const int i = i0 + lane;
-            tot += i < cnt ? ln_weight(B.st[B.open_list[i]].ng) : 0;
+            tot += i < cnt ? B.st[B.open_list[i]].ng + 1 : 0;
         }
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) tot += __shfl_xor(tot, o);
         int carry = 0, mine = -1, wn = 1;
         for (int i0 = 0; i0 < cnt && mine < 0; i0 += 64) {
             const int i = i0 + lane;
-            const int w = i < cnt ? ln_weight(B.st[B.open_list[i]].ng) : 0;
+            const int w = i < cnt ? B.st[B.open_list[i]].ng + 1 : 0;
             int incl = w;
 #pragma unroll
             for (int o = 1; o < 64; o <<= 1) {
@@ -1430,7 +1391,7 @@ ODO_INLINE void lanes_body(const RansacBufs& B, const RansacCfg& cfg, uint32_t* 
                     if (j < ns) {
                         const GoodPt g = P[smp[1 + j]];
                         if (tfc_point_ok(g)) {
-                            tf.add<EFAST && LN_TFAST>(g.sx, g.sy, g.sz, g.tx, g.ty, g.tz, g.w);
+                            tf.add<EFAST>(g.sx, g.sy, g.sz, g.tx, g.ty, g.tz, g.w);
                             nfit++;
                         }
                     }
@@ -1488,7 +1449,7 @@ ODO_INLINE void lanes_body(const RansacBufs& B, const RansacCfg& cfg, uint32_t* 
 #pragma unroll
                         for (int t = 0; t < 4; t++) {
                             const bool in = vj[t] && ((mine >> js[t]) & 1u);
-                            tf.add_sel<EFAST && LN_TFAST>(g4[t].sx, g4[t].sy, g4[t].sz, g4[t].tx, g4[t].ty, g4[t].tz,
+                            tf.add_sel<EFAST>(g4[t].sx, g4[t].sy, g4[t].sz, g4[t].tx, g4[t].ty, g4[t].tz,
                                                           g4[t].w, in);
                             nfit += in;
                         }
@@ -1515,24 +1476,15 @@ ODO_INLINE void lanes_body(const RansacBufs& B, const RansacCfg& cfg, uint32_t* 
             const int rank = (int)lane_rank(actm);  // this lane's slot among the active ones
             if (act) la[rank] = lane;
             // the active hypotheses' transforms in slot order, read back by the
-            // sweep as three broadcast 16-byte loads per slot instead of 12 permutes
+            // sweep as broadcast 16-byte loads per slot instead of permutes
             if (act) {
-                if (LN_TD) {
-                    double* tw = lTd + rank * LN_TW;
-                    double Z[6];
+                double* tw = lTd + rank * LN_TW;
+                double Z[6];
 #pragma unroll
-                    for (int i = 0; i < 12; i += 2) *reinterpret_cast<double2*>(tw + i) = double2{Td[i], Td[i + 1]};
-                    if (LN_TD == 1) {
-                        hyp_cov_terms(Td, K, Z);
+                for (int i = 0; i < 12; i += 2) *reinterpret_cast<double2*>(tw + i) = double2{Td[i], Td[i + 1]};
+                hyp_cov_terms(Td, K, Z);
 #pragma unroll
-                        for (int i = 0; i < 6; i += 2) *reinterpret_cast<double2*>(tw + 12 + i) = double2{Z[i], Z[i + 1]};
-                    }
-                } else {
-                    float4* tw = reinterpret_cast<float4*>(lT + rank * 12);
-                    tw[0] = make_float4(T[0], T[1], T[2], T[3]);
-                    tw[1] = make_float4(T[4], T[5], T[6], T[7]);
-                    tw[2] = make_float4(T[8], T[9], T[10], T[11]);
-                }
+                for (int i = 0; i < 6; i += 2) *reinterpret_cast<double2*>(tw + 12 + i) = double2{Z[i], Z[i + 1]};
             }
             wave_sync();
             double meanError = 0.0;
@@ -1549,22 +1501,13 @@ ODO_INLINE void lanes_body(const RansacBufs& B, const RansacCfg& cfg, uint32_t* 
                 for (int i = 0; i < nact; i += 2) {
                     const int a = i + hf;  // this half's hypothesis slot
                     double Ta[12];
-                    const double* Za = nullptr;
-                    if (LN_TD) {
-                        const double* tr = lTd + min(a, nact - 1) * LN_TW;
+                    const double* tr = lTd + min(a, nact - 1) * LN_TW;
 #pragma unroll
-                        for (int q = 0; q < 12; q += 2) {
-                            const double2 v = *reinterpret_cast<const double2*>(tr + q);
-                            Ta[q] = v.x, Ta[q + 1] = v.y;
-                        }
-                        if (LN_TD == 1) Za = tr + 12;
-                    } else {
-                        const float4* tr = reinterpret_cast<const float4*>(lT + min(a, nact - 1) * 12);
-                        const float4 t0 = tr[0], t1 = tr[1], t2 = tr[2];
-                        const float tf[12] = {t0.x, t0.y, t0.z, t0.w, t1.x, t1.y, t1.z, t1.w, t2.x, t2.y, t2.z, t2.w};
-#pragma unroll
-                        for (int q = 0; q < 12; q++) Ta[q] = tf[q];
+                    for (int q = 0; q < 12; q += 2) {
+                        const double2 v = *reinterpret_cast<const double2*>(tr + q);
+                        Ta[q] = v.x, Ta[q + 1] = v.y;
                     }
+                    const double* Za = tr + 12;
                     double d = -1.0;  // not an inlier
                     if (a < nact && !skip) {
                         const double e = error_function2_mk(x1, x2, Ta, K, Za, EFAST);
@@ -1686,12 +1629,12 @@ __global__ void __launch_bounds__(64 * LN_WAVES, 2) k_ransac_lanes(RansacBufs B,
     // puts lane r's row on banks 2r, 2r + 1
     __shared__ double s_res[LN_WAVES][LN_SLOTS * LN_RS];
     __shared__ int s_la[LN_WAVES][64];
-    __shared__ __attribute__((aligned(16))) double s_T[LN_WAVES][LN_SLOTS * LN_TW / (LN_TD ? 1 : 2)];  // active slots' transforms
+    __shared__ __attribute__((aligned(16))) double s_T[LN_WAVES][LN_SLOTS * LN_TW];  // active slots' transforms
     MahalConst K;
     K.raster_cov_x = cfg.raster_cov_x;
     K.raster_cov_y = cfg.raster_cov_y;
     K.depth_cov = *B.latch;
-    if (EF_FAST == 2 && __builtin_amdgcn_readfirstlane(B.open_cnt[2]) && ef_fast_cov(K))
+    if (__builtin_amdgcn_readfirstlane(B.open_cnt[2]) && ef_fast_cov(K))
         lanes_body<true>(B, cfg, lane_slab, waves_total, min_open, lane, wv, gw, s_pts[wv], s_res[wv], s_la[wv],
                          s_T[wv]);
     else
@@ -1982,8 +1925,8 @@ struct Layout {
     size_t gpts, st, hyp, samples, ready, masks, raw, open, lslab, total;
 };
 
-// k_ransac_lanes grid: workgroups of LN_WAVES waves (ODO_RANSAC_LANES, 0 = the
-// wave-per-hypothesis work list k_ransac_eval_list instead). 384 = 1.5 per CU
+// k_ransac_lanes grid: workgroups of LN_WAVES waves (ODO_RANSAC_LANES, at
+// least 1). 384 = 1.5 per CU
 // of the 256: alone the launch is faster at 2 per CU (512), but in the
 // pipelined step the half-empty CUs run the other pair stream's PnP and the
 // next batch's extraction beside it (hard workload +5 %)
@@ -1993,7 +1936,7 @@ struct Layout {
 static int ln_groups() {
     static int r = [] {
         const char* e = odo_knob("ODO_RANSAC_LANES");
-        return e ? std::max(0, atoi(e)) : LN_GROUPS;
+        return e ? std::max(1, atoi(e)) : LN_GROUPS;
     }();
     return r;
 }
@@ -2123,27 +2066,7 @@ void launch_ransac_raw(hipStream_t st, void* scratch, int npairs, int match_cap,
     hipLaunchKernelGGL(k_ransac_raw, dim3(npairs), dim3(64), 0, st, B, seed_base, pair_base, raw_jump_tables(L), L);
 }
 
-static int ev2_rows() {
-    static int r = [] {
-        const char* e = odo_knob("ODO_EV2_ROWS");
-        // default: every remaining hypothesis row in flight. A pair whose best
-        // inlier ratio stays just under the 80 % break visits ~all H
-        // hypotheses; fewer rows make it take several rounds (measured at
-        // 64-frame batches: 1.366 ms per step with all rows, 1.39 with 16)
-        return e ? std::max(1, atoi(e)) : 1 << 30;
-    }();
-    return r;
-}
-
-// workgroups of the work-list second launch (ODO_EV2_LIST; 0 = the
-// (pairs x rows) grid instead)
-static int ev2_list() {
-    static int r = [] {
-        const char* e = odo_knob("ODO_EV2_LIST");
-        return e ? std::max(0, atoi(e)) : 512;
-    }();
-    return r;
-}
+constexpr int EV2_LIST_GROUPS = 512;  // workgroups of the work-list second launch (k_ransac_eval_list)
 
 static void ransac_eval_lds_attr() {
     static bool done = false;
@@ -2239,45 +2162,40 @@ void launch_ransac(hipStream_t st, const void* good, const int* n_good, const in
         const int r0 = (h0 + EV_WAVES - 1) / EV_WAVES, nw = std::min(h0, EV_WAVES);
         hipLaunchKernelGGL(k_ransac_eval, dim3(npairs, r0), dim3(64 * nw), EV_LDS, st, B, cfg, 0, 0, h0);
     }
-    // the second launch's waves stride over the remaining hypotheses
-    // [h0, H): ev2_rows() rows of EV_WAVES per pair in flight (ODO_EV2_ROWS)
+    // the second launch takes the remaining hypotheses [h0, H), rows of
+    // EV_WAVES per pair
     const int rows = (H - h0 + EV_WAVES - 1) / EV_WAVES;
     if (rows > 0) {
-        if (ev2_list()) {
-            hipLaunchKernelGGL(k_ransac_open, dim3(1), dim3(256), 0, st, B, npairs);
-            // which of the two kernels takes the open pairs: decided on the
-            // host from the previous batch's open count on this frame set
-            // (open_hint, page-locked, copied back asynchronously), so
-            // only one of them is launched; both give the same results
-            // (no hint yet, -1: the first batch of a set: both are
-            // launched and the open count on the device picks one)
-            const int lanes = ln_groups();
-            const int tmin = cfg.lanes_min_open > 0 ? cfg.lanes_min_open : ln_min_open();
-            const int hint = open_hint ? *reinterpret_cast<volatile int*>(open_hint) : 0;
-            const bool use_lanes = lanes && open_hint && hint >= tmin;
-            // the pairs still open after the first launch are the long
-            // ones (the bench's sequence: 2 of 64, visiting 36 and 380
-            // hypotheses): the work list folds them with the whole wave
-            // (64 ready flags per load, try_fold_wave) instead of lane
-            // 0's serial coherent loads, ~0.4 us per visited hypothesis
-            RansacCfg cfg2 = cfg;
-            cfg2.fold_wave = EV2_FOLD_WAVE;
-            if (lanes && hint < 0) {
-                hipLaunchKernelGGL(k_ransac_eval_list, dim3(ev2_list()), dim3(64 * EV_WAVES), EV_LDS, st, B, cfg2,
-                                   h0, rows, tmin - 1);
-                hipLaunchKernelGGL(k_ransac_lanes, dim3(lanes), dim3(64 * LN_WAVES), 0, st, B, cfg, B.lslab,
-                                   lanes * LN_WAVES, tmin);
-            } else if (use_lanes)
-                hipLaunchKernelGGL(k_ransac_lanes, dim3(lanes), dim3(64 * LN_WAVES), 0, st, B, cfg, B.lslab,
-                                   lanes * LN_WAVES, 1);
-            else
-                hipLaunchKernelGGL(k_ransac_eval_list, dim3(ev2_list()), dim3(64 * EV_WAVES), EV_LDS, st, B, cfg2,
-                                   h0, rows, 1 << 30);
-            if (open_hint) (void)hipMemcpyAsync(open_hint, B.open_cnt, sizeof(int), hipMemcpyDeviceToHost, st);
-        } else {
-            hipLaunchKernelGGL(k_ransac_eval, dim3(npairs, std::min(rows, ev2_rows())), dim3(64 * EV_WAVES),
-                               EV_LDS, st, B, cfg, h0, 0, H);
-        }
+        hipLaunchKernelGGL(k_ransac_open, dim3(1), dim3(256), 0, st, B, npairs);
+        // which of the two kernels takes the open pairs: decided on the
+        // host from the previous batch's open count on this frame set
+        // (open_hint, page-locked, copied back asynchronously), so
+        // only one of them is launched; both give the same results
+        // (no hint yet, -1: the first batch of a set: both are
+        // launched and the open count on the device picks one)
+        const int lanes = ln_groups();
+        const int tmin = cfg.lanes_min_open > 0 ? cfg.lanes_min_open : ln_min_open();
+        const int hint = open_hint ? *reinterpret_cast<volatile int*>(open_hint) : 0;
+        const bool use_lanes = open_hint && hint >= tmin;
+        // the pairs still open after the first launch are the long
+        // ones (the bench's sequence: 2 of 64, visiting 36 and 380
+        // hypotheses): the work list folds them with the whole wave
+        // (64 ready flags per load, try_fold_wave) instead of lane
+        // 0's serial coherent loads, ~0.4 us per visited hypothesis
+        RansacCfg cfg2 = cfg;
+        cfg2.fold_wave = 1;
+        if (hint < 0) {
+            hipLaunchKernelGGL(k_ransac_eval_list, dim3(EV2_LIST_GROUPS), dim3(64 * EV_WAVES), EV_LDS, st, B, cfg2, h0,
+                               rows, tmin - 1);
+            hipLaunchKernelGGL(k_ransac_lanes, dim3(lanes), dim3(64 * LN_WAVES), 0, st, B, cfg, B.lslab,
+                               lanes * LN_WAVES, tmin);
+        } else if (use_lanes)
+            hipLaunchKernelGGL(k_ransac_lanes, dim3(lanes), dim3(64 * LN_WAVES), 0, st, B, cfg, B.lslab,
+                               lanes * LN_WAVES, 1);
+        else
+            hipLaunchKernelGGL(k_ransac_eval_list, dim3(EV2_LIST_GROUPS), dim3(64 * EV_WAVES), EV_LDS, st, B, cfg2, h0,
+                               rows, 1 << 30);
+        if (open_hint) (void)hipMemcpyAsync(open_hint, B.open_cnt, sizeof(int), hipMemcpyDeviceToHost, st);
     }
     hipLaunchKernelGGL(k_ransac_final, dim3(npairs), dim3(64), 0, st, B, cfg);
 }

@@ -241,11 +241,10 @@ struct odo_ctx {
     int* qcnt[NSETS] = {};
     int lm_words = 0;
     int knn_split = 2;  // kNN-2 train splits per query block (ODO_KNN_SPLIT): more waves for short query lists
-    // kNN-2 form (ODO_KNN_MFMA): 0 the VALU xor/popcount kernel k_knn2, 1 exact
-    // int8 sign-vector products on the matrix cores (k_knn2_mx), 2 the same on
-    // FP4 (e2m1 +-1) operands (k_knn2_f4, the default: 97 us vs 137-150 us for
-    // the 256-pair bench launch alone)
-    int knn_mx = KNN_FMT_F4;
+    // kNN-2 form (odo_kernel_forms.knn): true exact sign-vector products on the
+    // matrix cores with FP4 (e2m1 +-1) operands (k_knn2_f4, the default), false
+    // the VALU xor/popcount kernel k_knn2
+    bool knn_mx = true;
     int last_knn_set = -1, last_knn_n = 0;  // the most recent batch's kNN-2 launch (odo_knn_replay_time)
     uint64_t* sort_scratch = nullptr;
     double* latch = nullptr;
@@ -906,9 +905,8 @@ static int alloc_buffers(odo_ctx* c) {
     c->lm_words = (c->kp_cap + 31) / 32;
     // kernel forms (odo_config.forms; all bit-identical)
     if (c->cfg.forms.knn_split > 0) c->knn_split = std::min(8, c->cfg.forms.knn_split);
-    c->knn_mx = c->cfg.forms.knn == ODO_KNN_FORM_VALU ? KNN_FMT_VALU : KNN_FMT_F4;
+    c->knn_mx = c->cfg.forms.knn != ODO_KNN_FORM_VALU;
     if (const char* ks = odo_knob("ODO_KNN_SPLIT")) c->knn_split = std::min(8, std::max(1, atoi(ks)));
-    if (const char* km = odo_knob("ODO_KNN_MFMA")) c->knn_mx = std::min(2, std::max(0, atoi(km)));
     if (c->knn_mx) c->knn_split = 1;  // one top-2 slot per query
     for (int i = 0; i < NSETS; i++) {
         if ((e = dalloc(&c->knn_idx[i], (size_t)c->knn_split * B * c->kp_cap))) return e;
@@ -1228,14 +1226,6 @@ static bool build_pyramid(odo_ctx* c, hipStream_t st, const uint8_t* d_bgr, uint
                                           (c->pform == ODO_PYRAMID_FORM_AUTO && n >= PYR_FUSED_MIN_FRAMES));
     if (fused) {
         if (c->pform == ODO_PYRAMID_FORM_FUSED_NOBLUR || !c->blur_fusable) blur = nullptr;
-        static const bool gray_apart = [] {  // tuning: gray as its own launch before the fused levels
-            const char* e = odo_knob("ODO_PYR_GRAY");
-            return e && e[0] == '1';
-        }();
-        if (gray_apart && d_bgr) {
-            launch_gray(st, d_bgr, pyr, c->W, c->H, c->lv_h[0].pitch, (size_t)c->W * c->H * 3, P, n);
-            d_bgr = nullptr;
-        }
         launch_pyramid(st, d_bgr, pyr, (size_t)c->W * c->H * 3, P, c->lv, c->rx, c->ry, c->rx_off.data(),
                        c->ry_off.data(), c->nlevels, n, blur, c->lv_h.data(),
                        c->ry_h.data());
@@ -1470,8 +1460,8 @@ static void launch_set_knn2(odo_ctx* c, hipStream_t st, int s, int n) {
     const size_t KC = (size_t)c->kp_cap;
     const FrameSlot f = frame_at(c, fbase(c, s));
     if (c->knn_mx)
-        launch_knn2_mx(st, f.desc, f.nkp, KC * 32, f.desc + KC * 32, f.nkp + 1, KC * 32, c->knn_idx[s], c->knn_dist[s],
-                       KC, c->kp_cap, n, c->qlist[s], c->qcnt[s], KC, c->knn_mx);
+        launch_knn2_f4(st, f.desc, f.nkp, KC * 32, f.desc + KC * 32, f.nkp + 1, KC * 32, c->knn_idx[s], c->knn_dist[s],
+                       KC, c->kp_cap, n, c->qlist[s], c->qcnt[s], KC);
     else
         launch_knn2(st, f.desc, f.nkp, KC * 32, f.desc + KC * 32, f.nkp + 1, KC * 32, c->knn_idx[s], c->knn_dist[s],
                     KC, c->kp_cap, n, c->qlist[s], c->qcnt[s], KC, c->knn_split, (size_t)c->maxb * KC);
@@ -2193,8 +2183,8 @@ int odo_knn2_hamming(odo_ctx* c, const uint8_t* q, int nq, const uint8_t* t, int
     uint8_t* db = dall.as<uint8_t>();
     const DevView dq{db + o_q}, dt{db + o_t}, dn{db + o_n}, di{db + o_i}, dd{db + o_d};
     if (c->knn_mx && nt <= 8192)  // the packed key holds a 13-bit train index
-        launch_knn2_mx(st, dq.as<uint8_t>(), dn.as<int>(), 0, dt.as<uint8_t>(), dn.as<int>() + 1, 0, di.as<int2>(),
-                       dd.as<int2>(), 0, nq, 1, nullptr, nullptr, 0, c->knn_mx);
+        launch_knn2_f4(st, dq.as<uint8_t>(), dn.as<int>(), 0, dt.as<uint8_t>(), dn.as<int>() + 1, 0, di.as<int2>(),
+                       dd.as<int2>(), 0, nq, 1, nullptr, nullptr, 0);
     else
         launch_knn2(st, dq.as<uint8_t>(), dn.as<int>(), 0, dt.as<uint8_t>(), dn.as<int>() + 1, 0, di.as<int2>(),
                     dd.as<int2>(), 0, nq, 1);

@@ -208,7 +208,7 @@ ODO_INLINE float det3(const float M[3][3]) {
 // and the denominator in [2^-20, 2^40] (no operand scaling below an exponent
 // difference of 96, a normal quotient in (0, 1]): every weight a pair's TFC
 // adds in that range (k_ransac_prep's guard, RState.efast), a sum of at most
-// 2^20 of them (k_ransac_lanes' fast-form launch, LN_TFAST)
+// 2^20 of them (k_ransac_lanes' fast-form launch)
 template <bool FAST>
 ODO_INLINE float tfc_div(float a, float b) {
     if (!FAST) return a / b;
@@ -453,20 +453,17 @@ ODO_INLINE void hyp_cov_terms(const double T[12], const MahalConst& K, double Z[
     Z[4] = (T[10] * c22) * T[9];
     Z[5] = (T[10] * c22) * T[10];
 }
-#ifndef EF_FAST
 // ErrorFunction2's three square roots and three reciprocals (error_function2_mk)
 // as the cores of LLVM's correctly rounded AMDGPU f64 sequences without their
 // range fix-ups, which are inactive on the ranges below (ef_sqrt / ef_rcp).
-// 1: every evaluation in the fast form, redone with the IEEE sequences when an
-// operand falls outside them (bit-identical; costs k_ransac_lanes registers:
-// 187 VGPRs, which break its co-residency with k_pnp). 2 (default):
 // k_ransac_lanes picks the fast form once per launch when every open pair
 // passed k_ransac_prep's range guard (below), else the IEEE form;
-// k_ransac_eval / _eval_list pick it per pair (EV_EFAST; a wave holds one
-// pair, so the branch is uniform). Round 6, hard workload, 3 alternations each:
-// 53.1k vs 51.4k frames/s (profiles/r06_ef2); 46 parity tests green on it.
-#define EF_FAST 2
-#endif
+// k_ransac_eval / _eval_list pick it per pair (a wave holds one pair, so the
+// branch is uniform). Round 6, hard workload, 3 alternations each: 53.1k vs
+// 51.4k frames/s (profiles/r06_ef2); 46 parity tests green on it. (Taking the
+// fast form always and redoing a call whose operand left the ranges cost
+// k_ransac_lanes registers: 187 VGPRs, which break its co-residency with
+// k_pnp.)
 // sqrt: v_rsq_f64, then the Goldschmidt iteration and two corrections of
 // LLVM's lowering (its ldexp scaling only acts below 2^-767, its class test
 // only at 0 and +inf)
@@ -575,8 +572,8 @@ ODO_INLINE double error_function2_mk_t(const float x1[3], const float x2[3], con
     return r;
 }
 
-// EF_FAST == 2 (k_ransac_lanes, k_ransac_eval*): the fast form without the per-call
-// check, for pairs whose evaluated points all have depths in [2^-20, 2^20]
+// The fast form runs without a per-call check (k_ransac_lanes,
+// k_ransac_eval*), for pairs whose evaluated points all have depths in [2^-20, 2^20]
 // (ef_fast_pt, checked once per pair by k_ransac_prep: RState.efast) under a
 // DepthCovariance latch in [2^-200, 2^200] (ef_fast_cov). There every operand
 // lies in the ranges above whenever the result can be accepted: with C2 =
@@ -596,12 +593,8 @@ ODO_INLINE bool ef_fast_cov(const MahalConst& K) {
 }
 ODO_INLINE double error_function2_mk(const float x1[3], const float x2[3], const double T[12], const MahalConst& K,
                                      const double* Z = nullptr, bool fast = false) {
-    bool ok = true;
-    if (EF_FAST == 2) return fast ? error_function2_mk_t<true>(x1, x2, T, K, Z, ok)
-                                  : error_function2_mk_t<false>(x1, x2, T, K, Z, ok);
-    double r = error_function2_mk_t<EF_FAST != 0>(x1, x2, T, K, Z, ok);
-    if (EF_FAST == 1 && __builtin_expect(!ok, 0)) r = error_function2_mk_t<false>(x1, x2, T, K, Z, ok);
-    return r;
+    bool ok = true;  // the range checks of ef_sqrt / ef_rcp: covered by the pair's guard, not read
+    return fast ? error_function2_mk_t<true>(x1, x2, T, K, Z, ok) : error_function2_mk_t<false>(x1, x2, T, K, Z, ok);
 }
 
 // The shortcut of error_function2 (ransac.cpp:350-365): true when the point

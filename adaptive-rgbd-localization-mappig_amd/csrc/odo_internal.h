@@ -11,8 +11,8 @@
 
 namespace odo {
 
-// Measurement / A-B knobs (serial streams, stage skipping, retired kernel
-// forms, grid sizes). Only the tuning build (make tuning: -DODO_TUNING,
+// Measurement / A-B knobs (serial streams, stage skipping, grid sizes, the
+// choice among the kernel forms that ship). Only the tuning build (make tuning: -DODO_TUNING,
 // build_tuning/libodo_hip.so, selected with ODO_LIB) reads them from the
 // environment; the production library ignores the environment entirely, so a
 // stray variable cannot change (or invalidate) a production context.
@@ -246,14 +246,11 @@ void launch_knn2(hipStream_t st, const uint8_t* q, const int* qn, size_t q_strid
                  size_t t_stride, int2* idx, int2* dist, size_t out_stride, int max_q, int npairs,
                  const int32_t* qlist = nullptr, const int* qcnt = nullptr, size_t ql_stride = 0, int nsplit = 1,
                  size_t split_stride = 0);
-// the same top-2 on the matrix cores (exact int8 sign-vector formulation); one
-// split slot, all trains (k_knn2_mx)
-// kNN-2 kernel forms (ODO_KNN_MFMA): VALU xor/popcount, int8 MFMA, FP4 MFMA
-enum { KNN_FMT_VALU = 0, KNN_FMT_I8 = 1, KNN_FMT_F4 = 2 };
-void launch_knn2_mx(hipStream_t st, const uint8_t* q, const int* qn, size_t q_stride, const uint8_t* t, const int* tn,
+// the same top-2 on the matrix cores (exact FP4 sign-vector formulation); one
+// split slot, all trains, at most 8192 of them (k_knn2_f4)
+void launch_knn2_f4(hipStream_t st, const uint8_t* q, const int* qn, size_t q_stride, const uint8_t* t, const int* tn,
                     size_t t_stride, int2* idx, int2* dist, size_t out_stride, int max_q, int npairs,
-                    const int32_t* qlist = nullptr, const int* qcnt = nullptr, size_t ql_stride = 0,
-                    int fmt = KNN_FMT_I8);
+                    const int32_t* qlist = nullptr, const int* qcnt = nullptr, size_t ql_stride = 0);
 void launch_vo_lm(hipStream_t st, const float* xyz, const int* nkp, int kp_cap, int slot0, float th_depth_m,
                   uint32_t* lm_bits, int lm_words, int32_t* qlist, int* qcnt, int npairs);
 void launch_pair_match(hipStream_t st, const int2* knn_idx, const int2* knn_dist, size_t knn_stride, const float* xyz,

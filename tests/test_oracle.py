@@ -122,6 +122,10 @@ def test_fast_cell_kat():
                 cell = _fast_numpy(big[y0:y1, x0:x1], 7)
             exp += [(x + j * wc, y + i * hc, s) for x, y, s in cell]
     assert got == exp and len(exp) > 0
+    # the vectorised reference of extract_ref.py, on the same image
+    import extract_ref
+    x, y, r, _ = extract_ref.fast_level_ref(big, 20, 7)
+    assert list(zip(x.tolist(), y.tolist(), r.tolist())) == exp
 
 
 def test_blur_kat():

@@ -554,26 +554,92 @@ struct ONode {
 #define OT_THREADS 256  // threads per (frame, level) workgroup
 #endif
 
-// The workgroup's keys k = t, t + OT_THREADS, ... in batches of OT_KB per
-// thread: ld(k, u) issues a batch's global loads (keys / knode / kquad live in
-// HBM scratch) before pr(k, u) consumes them, so a pass over the keys waits
-// one memory latency per batch instead of one per key (round 5)
+// One pass over the workgroup's keys: thread t owns k = t + OT_THREADS * u and
+// f(k, key, node) may replace the key's node; no pass reads another thread's
+// key or node.
+//   RES   a workgroup of at most OT_THREADS * OT_KB keys: key and node of
+//         slot u stay in this thread's registers rk[u] / rn[u] from the
+//         gather to the output, and a pass touches no global memory.
+//   !RES  keys and nodes live in HBM scratch; a pass loads what LD names in
+//         batches of OT_KB per thread before it consumes them (one memory
+//         latency per batch instead of one per key, round 5) and stores the
+//         nodes that changed.
 #ifndef OT_KB
 #define OT_KB 8
 #endif
 #ifndef OT_RANK_MAX
 #define OT_RANK_MAX 512  // phase 2's node ranks counted (not sorted) up to this many entries
 #endif
-template <typename Ld, typename Pr>
-ODO_INLINE void ot_keys(int n, int t, Ld&& ld, Pr&& pr) {
-    for (int k0 = t; k0 < n; k0 += OT_THREADS * OT_KB) {
+enum { OT_LDK = 1, OT_LDN = 2 };
+template <bool RES, int LD, typename F>
+ODO_INLINE void ot_pass(int n, int t, uint32_t (&rk)[OT_KB], int (&rn)[OT_KB], const uint32_t* keys, int32_t* knode,
+                        F&& f) {
+    if constexpr (RES) {
 #pragma unroll
         for (int u = 0; u < OT_KB; u++)
-            if (k0 + u * OT_THREADS < n) ld(k0 + u * OT_THREADS, u);
+            if (t + u * OT_THREADS < n) f(t + u * OT_THREADS, rk[u], rn[u]);
+    } else {
+        for (int k0 = t; k0 < n; k0 += OT_THREADS * OT_KB) {
 #pragma unroll
-        for (int u = 0; u < OT_KB; u++)
-            if (k0 + u * OT_THREADS < n) pr(k0 + u * OT_THREADS, u);
+            for (int u = 0; u < OT_KB; u++) {
+                const int k = k0 + u * OT_THREADS;
+                rn[u] = -1;
+                if (k < n) {
+                    if (LD & OT_LDK) rk[u] = keys[k];
+                    if (LD & OT_LDN) rn[u] = knode[k];
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < OT_KB; u++) {
+                const int k = k0 + u * OT_THREADS;
+                if (k < n) {
+                    int node = rn[u];
+                    f(k, rk[u], node);
+                    if (node != rn[u]) knode[k] = node;
+                }
+            }
+        }
     }
+}
+
+ODO_INLINE int block_exclusive_scan(int v, int* tmp, int* total);
+
+// The candidates of cells [cell0, cell0 + nc) in cell order to dst[0..) (those
+// at cap and beyond are dropped); returns their number.
+ODO_INLINE int ot_gather(const uint32_t* __restrict__ cand, const int* __restrict__ cand_cnt, size_t cell0, int nc,
+                         int cell_cap, uint32_t* dst, int cap, int* scan) {
+    const int t = threadIdx.x;
+    int n = 0;
+    for (int cb = 0; cb < nc; cb += OT_THREADS) {
+        const int c = cb + t;
+        const int cnt = c < nc ? cand_cnt[cell0 + c] : 0;
+        int tot;
+        const int ex = block_exclusive_scan(cnt, scan, &tot);
+        if (c < nc) {
+            // 32 candidates in flight per batch (cell rows are 16-byte aligned):
+            // a load-then-store loop would wait out one memory latency per 4 keys
+            const uint4* src = reinterpret_cast<const uint4*>(cand + (cell0 + c) * cell_cap);
+            uint32_t* d = dst + n + ex;
+            const int room = cap - (n + ex);
+            const int m = cnt < room ? cnt : room;
+            for (int k0 = 0; k0 < m; k0 += 32) {
+                uint4 v[8];
+#pragma unroll
+                for (int u = 0; u < 8; u++)
+                    if (k0 + 4 * u < m) v[u] = src[(k0 >> 2) + u];
+#pragma unroll
+                for (int u = 0; u < 8; u++) {
+                    const int k = k0 + 4 * u;
+                    if (k < m) d[k] = v[u].x;
+                    if (k + 1 < m) d[k + 1] = v[u].y;
+                    if (k + 2 < m) d[k + 2] = v[u].z;
+                    if (k + 3 < m) d[k + 3] = v[u].w;
+                }
+            }
+        }
+        n += tot;
+    }
+    return n;
 }
 
 // vSizeAndPointerToNode entry: sorts by (size, creation seq); low 16 bits carry
@@ -622,24 +688,15 @@ ODO_INLINE int2 block_exclusive_scan2(int a, int b, int* tmp, int2* total) {
     return int2{ba + xa - a, bb + xb - b};
 }
 
-__global__ void __launch_bounds__(OT_THREADS) k_octree(const uint32_t* __restrict__ cand,
-                                                       const int* __restrict__ cand_cnt, const LevelDesc* __restrict__ lv,
-                                                       int ncells, int cell_cap, int nlevels,
-                                                       uint32_t* __restrict__ keys_g, int32_t* __restrict__ knode_g,
-                                                       uint8_t* __restrict__ kquad_g, size_t keys_stride_frame,
-                                                       uint32_t* __restrict__ okp, int* __restrict__ ocnt, int okp_stride,
-                                                       int node_cap) {
-    EXTRACT_PRIO();
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    // grid (levels, frames). Measured and retired: (frames, levels), every
-    // frame's level 0 (the longest workgroups) dispatched first: 129 vs
-    // 190-206 us alone, but the step slower (110.8 k vs 113.5 k frames/s,
-    // profiles/r02_octree_ab/): 256 level-0 workgroups at once crowd out the
-    // co-running pair stages.
-    const int f = blockIdx.y;
-    const int l = blockIdx.x;
+// The tree over the n > 0 gathered keys of one (frame, level) and the best key
+// of every final node to out[]. The keys are in rk[] (RES, see ot_pass) or in
+// keys[]; a key's node is its position in the current list, with the quadrant
+// it falls into (bits 16-17) between an iteration's classify and remap passes.
+template <bool RES>
+ODO_INLINE void ot_tree(const int n, const LevelDesc& L, char* smem, int* s_vars, const int node_cap,
+                        uint32_t (&rk)[OT_KB], int (&rn)[OT_KB], const uint32_t* keys, int32_t* knode,
+                        uint32_t* __restrict__ out, int* __restrict__ ocnt_fl, const int cap) {
     const int t = threadIdx.x;
-    const LevelDesc L = lv[l];
     // carve LDS
     ONode* nodesA = reinterpret_cast<ONode*>(smem);
     ONode* nodesB = nodesA + node_cap;
@@ -648,7 +705,6 @@ __global__ void __launch_bounds__(OT_THREADS) k_octree(const uint32_t* __restric
     int* iscr = npos + 4 * node_cap;                               // node_cap ints scratch
     int* scan = iscr + node_cap;                                   // OT_THREADS
     uint64_t* sortk = reinterpret_cast<uint64_t*>(scan + OT_THREADS + 2);  // node_cap (pow2) sort keys
-    __shared__ __attribute__((aligned(16))) int s_vars[16];
     int& s_J = s_vars[6];
     int& s_size = s_vars[0];
     int& s_prev = s_vars[1];
@@ -657,47 +713,6 @@ __global__ void __launch_bounds__(OT_THREADS) k_octree(const uint32_t* __restric
     int& s_finish = s_vars[4];
     int& s_vcnt = s_vars[5];
 
-    const size_t kbase = (size_t)f * keys_stride_frame + (size_t)L.key_off;
-    uint32_t* keys = keys_g + kbase;
-    int32_t* knode = knode_g + kbase;
-    uint8_t* kquad = kquad_g + kbase;
-    uint32_t* out = okp + ((size_t)f * nlevels + l) * okp_stride;
-
-    // ---- gather candidates of this level's cells in cell order
-    const int c0 = L.cell_begin, nc = L.cell_end - L.cell_begin;
-    int n = 0;
-    for (int cb = 0; cb < nc; cb += OT_THREADS) {
-        const int c = cb + t;
-        const int cnt = c < nc ? cand_cnt[(size_t)f * ncells + c0 + c] : 0;
-        int tot;
-        const int ex = block_exclusive_scan(cnt, scan, &tot);
-        if (c < nc) {
-            // 32 candidates in flight per batch (cell rows are 16-byte aligned):
-            // a load-then-store loop would wait out one memory latency per 4 keys
-            const uint4* src = reinterpret_cast<const uint4*>(cand + ((size_t)f * ncells + c0 + c) * cell_cap);
-            uint32_t* dst = keys + n + ex;
-            for (int k0 = 0; k0 < cnt; k0 += 32) {
-                uint4 v[8];
-#pragma unroll
-                for (int u = 0; u < 8; u++)
-                    if (k0 + 4 * u < cnt) v[u] = src[(k0 >> 2) + u];
-#pragma unroll
-                for (int u = 0; u < 8; u++) {
-                    const int k = k0 + 4 * u;
-                    if (k < cnt) dst[k] = v[u].x;
-                    if (k + 1 < cnt) dst[k + 1] = v[u].y;
-                    if (k + 2 < cnt) dst[k + 2] = v[u].z;
-                    if (k + 3 < cnt) dst[k + 3] = v[u].w;
-                }
-            }
-        }
-        n += tot;
-    }
-    __syncthreads();
-    if (n == 0) {
-        if (t == 0) ocnt[f * nlevels + l] = 0;
-        return;
-    }
     const int minX = 16, maxX = L.w - 16, minY = 16, maxY = L.h - 16;
     const int N = L.quota;
     const int nIni = (int)roundf((float)(maxX - minX) / (float)(maxY - minY));
@@ -715,20 +730,16 @@ __global__ void __launch_bounds__(OT_THREADS) k_octree(const uint32_t* __restric
         nodesA[i] = nd;
     }
     __syncthreads();
-    uint32_t ky[OT_KB];
-    int nd[OT_KB];
-    uint8_t kq[OT_KB];
     // the initial nodes' key counts: nIni is 1-2 for 4:3 frames, so every
     // key's atomic hit the same one or two LDS words (a 64-way serialised
     // atomic per key batch); the first four nodes are counted in registers
     // and added once per thread (the same integer counts)
     int ic0 = 0, ic1 = 0, ic2 = 0, ic3 = 0;
-    ot_keys(
-        n, t, [&](int k, int u) { ky[u] = keys[k]; },
-        [&](int k, int u) {
-            const float x = (float)(ky[u] & 0xfff);
+    ot_pass<RES, OT_LDK>(
+        n, t, rk, rn, keys, knode, [&](int k, uint32_t key, int& node) {
+            const float x = (float)(key & 0xfff);
             const int ni = (int)(x / hX);
-            knode[k] = ni;
+            node = ni;
             ic0 += ni == 0;
             ic1 += ni == 1;
             ic2 += ni == 2;
@@ -756,8 +767,7 @@ __global__ void __launch_bounds__(OT_THREADS) k_octree(const uint32_t* __restric
         s_phase = 1;
     }
     __syncthreads();
-    ot_keys(
-        n, t, [&](int k, int u) { nd[u] = knode[k]; }, [&](int k, int u) { knode[k] = iscr[nd[u]]; });
+    ot_pass<RES, OT_LDN>(n, t, rk, rn, keys, knode, [&](int k, uint32_t key, int& node) { node = iscr[node]; });
     for (int i = t; i < s_size; i += OT_THREADS) nodesA[i] = nodesB[i];
     __syncthreads();
 
@@ -772,21 +782,16 @@ __global__ void __launch_bounds__(OT_THREADS) k_octree(const uint32_t* __restric
             // ---------------- phase 1: divide every node with >1 keys
             for (int i = t; i < 4 * S; i += OT_THREADS) cc[i] = 0;
             __syncthreads();
-            ot_keys(
-                n, t,
-                [&](int k, int u) {
-                    nd[u] = knode[k];
-                    ky[u] = keys[k];
-                },
-                [&](int k, int u) {
-                    const ONode N0 = cur[nd[u]];
+            ot_pass<RES, OT_LDK | OT_LDN>(
+                n, t, rk, rn, keys, knode, [&](int k, uint32_t key, int& node) {
+                    const ONode N0 = cur[node];
                     if (N0.cnt > 1) {
-                        const int x = ky[u] & 0xfff, y = (ky[u] >> 12) & 0xfff;
+                        const int x = key & 0xfff, y = (key >> 12) & 0xfff;
                         const int hx = (N0.x1 - N0.x0 + 1) >> 1;  // ceil((x1-x0)/2), x1>=x0
                         const int hy = (N0.y1 - N0.y0 + 1) >> 1;
                         const int q = (x < N0.x0 + hx) ? (y < N0.y0 + hy ? 0 : 2) : (y < N0.y0 + hy ? 1 : 3);
-                        kquad[k] = (uint8_t)q;
-                        atomicAdd(&cc[nd[u] * 4 + q], 1);
+                        atomicAdd(&cc[node * 4 + q], 1);
+                        node |= q << 16;
                     }
                 });
             __syncthreads();
@@ -871,14 +876,11 @@ __global__ void __launch_bounds__(OT_THREADS) k_octree(const uint32_t* __restric
                 }
             }
             __syncthreads();
-            ot_keys(
-                n, t,
-                [&](int k, int u) {
-                    nd[u] = knode[k];
-                    kq[u] = kquad[k];
-                },
-                [&](int k, int u) { knode[k] = cc[nd[u] * 4 + (cur[nd[u]].cnt > 1 ? kq[u] : 0)]; });
-            __syncthreads();
+            // an undivided node's keys carry quadrant 0: cc[4 i] is its new position
+            ot_pass<RES, OT_LDN>(n, t, rk, rn, keys, knode, [&](int k, uint32_t key, int& node) {
+                node = cc[(node & 0xFFFF) * 4 + (node >> 16)];
+            });
+            // (every read of the s_ values in this iteration is behind a barrier)
             if (t == 0) {
                 s_prev = S;
                 s_size = newSize;
@@ -888,7 +890,6 @@ __global__ void __launch_bounds__(OT_THREADS) k_octree(const uint32_t* __restric
                 else if (newSize + expBase * 3 > N) s_phase = 2;
             }
             vcount = expBase;
-            __syncthreads();
             ONode* tmpp = cur;
             cur = nxt;
             nxt = tmpp;
@@ -944,21 +945,16 @@ __global__ void __launch_bounds__(OT_THREADS) k_octree(const uint32_t* __restric
             }
             for (int i = t; i < 4 * S; i += OT_THREADS) cc[i] = 0;
             __syncthreads();
-            ot_keys(
-                n, t,
-                [&](int k, int u) {
-                    nd[u] = knode[k];
-                    ky[u] = keys[k];
-                },
-                [&](int k, int u) {
-                    if (iscr[nd[u]] >= 0) {
-                        const ONode N0 = cur[nd[u]];
-                        const int x = ky[u] & 0xfff, y = (ky[u] >> 12) & 0xfff;
+            ot_pass<RES, OT_LDK | OT_LDN>(
+                n, t, rk, rn, keys, knode, [&](int k, uint32_t key, int& node) {
+                    if (iscr[node] >= 0) {
+                        const ONode N0 = cur[node];
+                        const int x = key & 0xfff, y = (key >> 12) & 0xfff;
                         const int hx = (N0.x1 - N0.x0 + 1) >> 1;
                         const int hy = (N0.y1 - N0.y0 + 1) >> 1;
                         const int q = (x < N0.x0 + hx) ? (y < N0.y0 + hy ? 0 : 2) : (y < N0.y0 + hy ? 1 : 3);
-                        kquad[k] = (uint8_t)q;
-                        atomicAdd(&cc[nd[u] * 4 + q], 1);
+                        atomicAdd(&cc[node * 4 + q], 1);
+                        node |= q << 16;
                     }
                 });
             __syncthreads();
@@ -1066,42 +1062,90 @@ __global__ void __launch_bounds__(OT_THREADS) k_octree(const uint32_t* __restric
                 if (size >= N || size == S) s_finish = 1;
             }
             __syncthreads();
-            ot_keys(
-                n, t,
-                [&](int k, int u) {
-                    nd[u] = knode[k];
-                    kq[u] = kquad[k];
-                },
-                [&](int k, int u) {
-                    const int is = iscr[nd[u]];
-                    knode[k] = cc[nd[u] * 4 + (is == -2 || is == -1 ? 0 : kq[u])];
-                });
-            __syncthreads();
+            // survivors (iscr -1: not listed, -2: listed, not divided) moved to cc[4 i]
+            ot_pass<RES, OT_LDN>(n, t, rk, rn, keys, knode, [&](int k, uint32_t key, int& node) {
+                const int i = node & 0xFFFF;
+                node = cc[i * 4 + (iscr[i] < 0 ? 0 : node >> 16)];
+            });
             ONode* tmpp = cur;
             cur = nxt;
             nxt = tmpp;
         }
         __syncthreads();
     }
-    // ---- retain best key per node (max response, first in candidate order)
+    // ---- retain best key per node (max response, first in candidate order):
+    // the keys (response, 0x7FFFFF - k) are unique, so the one key that finds
+    // its own value in best[node] is the node's winner and writes it
     const int S = s_size;
     unsigned* best = reinterpret_cast<unsigned*>(cc);
     for (int i = t; i < S; i += OT_THREADS) best[i] = 0;
     __syncthreads();
-    ot_keys(
-        n, t,
-        [&](int k, int u) {
-            ky[u] = keys[k];
-            nd[u] = knode[k];
-        },
-        [&](int k, int u) { atomicMax(&best[nd[u]], ((ky[u] >> 24) << 23) | (0x7FFFFFu - (unsigned)k)); });
+    ot_pass<RES, OT_LDK | OT_LDN>(n, t, rk, rn, keys, knode, [&](int k, uint32_t key, int& node) {
+        atomicMax(&best[node], ((key >> 24) << 23) | (0x7FFFFFu - (unsigned)k));
+    });
     __syncthreads();
-    const int cap = okp_stride;
-    for (int i = t; i < S && i < cap; i += OT_THREADS) {
-        const int k = 0x7FFFFF - (int)(best[i] & 0x7FFFFF);
-        out[i] = keys[k];
+    ot_pass<RES, OT_LDK | OT_LDN>(n, t, rk, rn, keys, knode, [&](int k, uint32_t key, int& node) {
+        if (node < cap && best[node] == (((key >> 24) << 23) | (0x7FFFFFu - (unsigned)k))) out[node] = key;
+    });
+    if (t == 0) *ocnt_fl = S < cap ? S : cap;
+}
+
+__global__ void __launch_bounds__(OT_THREADS) k_octree(const uint32_t* __restrict__ cand,
+                                                       const int* __restrict__ cand_cnt, const LevelDesc* __restrict__ lv,
+                                                       int ncells, int cell_cap, int nlevels,
+                                                       uint32_t* __restrict__ keys_g, int32_t* __restrict__ knode_g,
+                                                       size_t keys_stride_frame, uint32_t* __restrict__ okp,
+                                                       int* __restrict__ ocnt, int okp_stride, int node_cap) {
+    EXTRACT_PRIO();
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    __shared__ __attribute__((aligned(16))) int s_vars[16];
+    // grid (levels, frames). Measured and retired: (frames, levels), every
+    // frame's level 0 (the longest workgroups) dispatched first: 129 vs
+    // 190-206 us alone, but the step slower (110.8 k vs 113.5 k frames/s,
+    // profiles/r02_octree_ab/): 256 level-0 workgroups at once crowd out the
+    // co-running pair stages.
+    // The level is rotated by the frame: workgroups are dealt to the 8 XCDs
+    // round-robin in linear order, so with 8 levels and l = blockIdx.x every
+    // level-0 workgroup (the most keys, the largest quota) ran on the same
+    // XCD, 8 per CU in two rounds, while the others idled.
+    const int f = blockIdx.y;
+    const int l = (blockIdx.x + blockIdx.y) % nlevels;
+    const int t = threadIdx.x;
+    const LevelDesc L = lv[l];
+    uint32_t* out = okp + ((size_t)f * nlevels + l) * okp_stride;
+    int* ocnt_fl = ocnt + f * nlevels + l;
+    const size_t cell0 = (size_t)f * ncells + L.cell_begin;
+    const int nc = L.cell_end - L.cell_begin;
+    // ot_tree's scan scratch; the node arrays below it (16 bytes per node
+    // each: two lists, child counts, child positions) are free until the tree
+    // starts and stage the gathered keys of a resident workgroup
+    int* scan = reinterpret_cast<int*>(smem) + 17 * node_cap;
+    uint32_t* stage = reinterpret_cast<uint32_t*>(smem);
+    const int res_cap = min(OT_THREADS * OT_KB, 16 * node_cap);
+    uint32_t rk[OT_KB];
+    int rn[OT_KB];
+
+    // ---- gather candidates of this level's cells in cell order
+    const int n = ot_gather(cand, cand_cnt, cell0, nc, cell_cap, stage, res_cap, scan);
+    __syncthreads();
+    if (n == 0) {
+        if (t == 0) *ocnt_fl = 0;
+        return;
     }
-    if (t == 0) ocnt[f * nlevels + l] = S < cap ? S : cap;
+    if (n <= res_cap) {
+#pragma unroll
+        for (int u = 0; u < OT_KB; u++)
+            if (t + u * OT_THREADS < n) rk[u] = stage[t + u * OT_THREADS];
+        __syncthreads();  // the staging area becomes the node lists
+        ot_tree<true>(n, L, smem, s_vars, node_cap, rk, rn, nullptr, nullptr, out, ocnt_fl, okp_stride);
+    } else {
+        // more keys than the registers hold: keys and nodes in HBM scratch
+        const size_t kbase = (size_t)f * keys_stride_frame + (size_t)L.key_off;
+        ot_gather(cand, cand_cnt, cell0, nc, cell_cap, keys_g + kbase, 0x7FFFFFFF, scan);
+        __syncthreads();
+        ot_tree<false>(n, L, smem, s_vars, node_cap, rk, rn, keys_g + kbase, knode_g + kbase, out, ocnt_fl,
+                       okp_stride);
+    }
 }
 
 // ============================================================ blur
@@ -1876,11 +1920,11 @@ void launch_fast(hipStream_t st, const uint8_t* pyr, size_t pyr_stride, const Fa
 }
 size_t octree_lds_bytes(int node_cap) { return (size_t)76 * node_cap + 1032; }
 void launch_octree(hipStream_t st, const uint32_t* cand, const int* cand_cnt, const LevelDesc* lv, int ncells,
-                   int cell_cap, int nlevels, uint32_t* keys, int32_t* knode, uint8_t* kquad, size_t keys_stride,
+                   int cell_cap, int nlevels, uint32_t* keys, int32_t* knode, size_t keys_stride,
                    uint32_t* okp, int* ocnt, int okp_stride, int node_cap, int nframes) {
     const dim3 g(nlevels, nframes);
     hipLaunchKernelGGL(k_octree, g, dim3(OT_THREADS), octree_lds_bytes(node_cap), st, cand, cand_cnt, lv, ncells,
-                       cell_cap, nlevels, keys, knode, kquad, keys_stride, okp, ocnt, okp_stride, node_cap);
+                       cell_cap, nlevels, keys, knode, keys_stride, okp, ocnt, okp_stride, node_cap);
 }
 void launch_blur(hipStream_t st, const uint8_t* pyr, uint8_t* blur, size_t pyr_stride, const LevelDesc* lv,
                  const LevelDesc* lv_host, int nlevels, int nframes) {

@@ -199,7 +199,6 @@ struct odo_ctx {
     int* cand_cnt = nullptr;
     uint32_t* keys = nullptr;
     int32_t* knode = nullptr;
-    uint8_t* kquad = nullptr;
     uint32_t* okp = nullptr;
     int* ocnt = nullptr;
     orb_kp* kps = nullptr;
@@ -424,7 +423,7 @@ static int sync_all(odo_ctx* c) {
 static void free_ctx(odo_ctx* c) {
     if (!c) return;
     free_hyp_session(c->hs);
-    void* ptrs[] = {c->lv, c->cells, c->fsegs, c->rx, c->ry, c->pyr, c->blur, c->cand, c->cand_cnt, c->keys, c->knode, c->kquad,
+    void* ptrs[] = {c->lv, c->cells, c->fsegs, c->rx, c->ry, c->pyr, c->blur, c->cand, c->cand_cnt, c->keys, c->knode,
                     c->okp, c->ocnt, c->kps, c->desc, c->kun, c->xyz, c->ur, c->nkp, c->bgr_in[0], c->depth_in[0],
                     c->bgr_in[1], c->depth_in[1],
                     c->sort_scratch, c->latch, c->masks, c->adc, c->adb, c->smap, c->acand, c->abig, c->acell,
@@ -889,7 +888,6 @@ static int alloc_buffers(odo_ctx* c) {
     if ((e = dalloc(&c->cand_cnt, S * c->ncells))) return e;
     if ((e = dalloc(&c->keys, S * c->keys_per_frame))) return e;
     if ((e = dalloc(&c->knode, S * c->keys_per_frame))) return e;
-    if ((e = dalloc(&c->kquad, S * c->keys_per_frame))) return e;
     if ((e = dalloc(&c->okp, S * c->nlevels * c->okp_stride))) return e;
     if ((e = dalloc(&c->ocnt, S * c->nlevels))) return e;
     if ((e = dalloc(&c->kps, S * c->kp_cap))) return e;
@@ -1334,8 +1332,7 @@ static int run_extract(odo_ctx* c, int set, const uint8_t* d_bgr, const uint16_t
     tmark(c, 2, st);
     launch_octree(st, c->cand + (size_t)slot * c->ncells * c->cell_cap, c->cand_cnt + (size_t)slot * c->ncells, c->lv,
                   c->ncells, c->cell_cap, c->nlevels, c->keys + (size_t)slot * c->keys_per_frame,
-                  c->knode + (size_t)slot * c->keys_per_frame, c->kquad + (size_t)slot * c->keys_per_frame,
-                  c->keys_per_frame, c->okp + (size_t)slot * c->nlevels * c->okp_stride,
+                  c->knode + (size_t)slot * c->keys_per_frame, c->keys_per_frame, c->okp + (size_t)slot * c->nlevels * c->okp_stride,
                   c->ocnt + (size_t)slot * c->nlevels, c->okp_stride, c->node_cap, n);
     tmark(c, 3, st);
     if (!blur_done) launch_blur(st, pyr, c->blur + (size_t)slot * P, P, c->lv, c->lv_h.data(), c->nlevels, n);

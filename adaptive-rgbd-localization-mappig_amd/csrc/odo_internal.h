@@ -230,7 +230,7 @@ void launch_fast(hipStream_t st, const uint8_t* pyr, size_t pyr_stride, const Fa
 bool fast_lds_plan(const FastSeg* segs, int nsegs, FastLds& L);
 size_t octree_lds_bytes(int node_cap);
 void launch_octree(hipStream_t st, const uint32_t* cand, const int* cand_cnt, const LevelDesc* lv, int ncells,
-                   int cell_cap, int nlevels, uint32_t* keys, int32_t* knode, uint8_t* kquad, size_t keys_stride,
+                   int cell_cap, int nlevels, uint32_t* keys, int32_t* knode, size_t keys_stride,
                    uint32_t* okp, int* ocnt, int okp_stride, int node_cap, int nframes);
 void launch_blur(hipStream_t st, const uint8_t* pyr, uint8_t* blur, size_t pyr_stride, const LevelDesc* lv,
                  const LevelDesc* lv_host, int nlevels, int nframes);

@@ -15,13 +15,15 @@ from . import _abi
 from ._abi import (DETECTOR_ADAPTIVE_FAST, DETECTOR_ADAPTIVE_ORB, DETECTOR_ORB_SLAM2, KNN_FORM_FP4, KNN_FORM_VALU,
                    PYRAMID_FORM_AUTO, PYRAMID_FORM_CHAIN, PYRAMID_FORM_FUSED, PYRAMID_FORM_FUSED_NOBLUR,
                    AdaptiveParams, Calib, Config, DMatch, PnPRansacResult,
-                   DMATCH_DTYPE, KP_DTYPE, OrbParams, PAIR_DTYPE, PairResult, RansacParams, Rng, check, load, ptr)
+                   DMATCH_DTYPE, KP_DTYPE, OrbParams, PAIR_DTYPE, PairResult, RansacParams, Rng, check, load, ptr,
+                   ODOMETRY_ADAPTIVE_RBA, ODOMETRY_ADAPTIVE_RICP, ODOMETRY_RANSAC, RicpParams, RicpResult)
 
 __all__ = ["Odometry", "HostFrames", "PinnedResults", "default_config", "load", "KP_DTYPE", "DMATCH_DTYPE", "PAIR_DTYPE", "rng_stream",
            "kabsch", "Calib", "OrbParams", "RansacParams", "Config", "AdaptiveParams", "DETECTOR_ORB_SLAM2",
            "DETECTOR_ADAPTIVE_FAST", "DETECTOR_ADAPTIVE_ORB", "KNN_FORM_FP4", "KNN_FORM_VALU",
            "PYRAMID_FORM_AUTO", "PYRAMID_FORM_FUSED", "PYRAMID_FORM_CHAIN",
-           "PYRAMID_FORM_FUSED_NOBLUR"]
+           "PYRAMID_FORM_FUSED_NOBLUR", "ODOMETRY_ADAPTIVE_RBA", "ODOMETRY_RANSAC", "ODOMETRY_ADAPTIVE_RICP",
+           "RicpParams", "RicpResult", "default_ricp_params"]
 
 
 def default_config(width=640, height=480, max_batch=1, nfeatures=1000, iterations=200, seed=0x5EED0000,
@@ -46,6 +48,13 @@ def default_config(width=640, height=480, max_batch=1, nfeatures=1000, iteration
     for k, v in (forms or {}).items():  # odo_kernel_forms: bit-identical kernel alternatives
         setattr(cfg.forms, k, v)
     return cfg
+
+
+def default_ricp_params() -> RicpParams:
+    """odo_default_ricp_params: the constants of odometry.cpp:15, 52-53."""
+    p = RicpParams()
+    load().odo_default_ricp_params(ptr(p))
+    return p
 
 
 class HostFrames:
@@ -146,6 +155,38 @@ class Odometry:
     @property
     def latch(self) -> float:
         return self.lib.odo_get_latch(self.h)
+
+    def set_odometry(self, mode: int, **params):
+        """odo_set_odometry: the Odometry::Compute back-end of every track_batch*
+        call from the next batch on (ODOMETRY_ADAPTIVE_RBA, ODOMETRY_RANSAC,
+        ODOMETRY_ADAPTIVE_RICP). params: odo_ricp_params fields that differ
+        from the reference's constants (min_inliers, rmse_scale, refine_at,
+        reset_at, gicp_iterations, gicp_max_corr_dist)."""
+        p = default_ricp_params()
+        for k, v in params.items():
+            if k not in dict(RicpParams._fields_):
+                raise TypeError(f"odo_ricp_params has no field {k!r}")
+            setattr(p, k, v)
+        check(self.lib.odo_set_odometry(self.h, int(mode), ptr(p)))
+
+    def odometry_mode(self) -> int:
+        r = self.lib.odo_get_odometry(self.h)
+        if r < 0:
+            check(r)
+        return r
+
+    def ricp(self, i: int):
+        """odo_get_ricp: what ADAPTIVE_RICP did for pair i of the last batch.
+        Returns dict(T12 4x4, branch, converged, iterations, n_corr, n_cloud,
+        src n_cloud x 3, tgt n_cloud x 3): the record and Ransac's
+        mpSourceCloud / mpTargetCloud."""
+        r = RicpResult()
+        src = np.zeros((self.kp_cap, 3), np.float32)
+        tgt = np.zeros((self.kp_cap, 3), np.float32)
+        check(self.lib.odo_get_ricp(self.h, i, ptr(r), ptr(src), ptr(tgt), self.kp_cap))
+        n = r.n_cloud
+        return dict(T12=np.array(r.T12, np.float32).reshape(4, 4), branch=r.branch, converged=r.converged,
+                    iterations=r.iterations, n_corr=r.n_corr, n_cloud=n, src=src[:n].copy(), tgt=tgt[:n].copy())
 
     def track_batch(self, bgr_ptr: int, depth_ptr: int, n: int, want_results=True):
         """Device-resident inputs (e.g. torch tensor .data_ptr())."""

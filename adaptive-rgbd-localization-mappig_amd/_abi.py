@@ -67,6 +67,24 @@ class PairResult(C.Structure):
                 ("n_queries", C.c_int32), ("n_sweeps", C.c_int32), ("n_fit_points", C.c_int32)]
 
 
+class RicpParams(C.Structure):
+    """odo_ricp_params (include/odo_types.h): odometry.cpp:15, 52-53."""
+    _fields_ = [("min_inliers", C.c_int32), ("rmse_scale", C.c_float), ("refine_at", C.c_float),
+                ("reset_at", C.c_float), ("gicp_iterations", C.c_int32), ("gicp_max_corr_dist", C.c_double)]
+
+
+class RicpResult(C.Structure):
+    """odo_ricp_result (include/odo_types.h)."""
+    _fields_ = [("T12", C.c_float * 16), ("branch", C.c_int32), ("converged", C.c_int32),
+                ("iterations", C.c_int32), ("n_corr", C.c_int32), ("n_cloud", C.c_int32), ("pad", C.c_int32 * 3)]
+
+
+ODOMETRY_ADAPTIVE_RBA = 0   # include/odo.h ODO_ODOMETRY_ADAPTIVE_RBA
+ODOMETRY_RANSAC = 1         # include/odo.h ODO_ODOMETRY_RANSAC
+ODOMETRY_ADAPTIVE_RICP = 2  # include/odo.h ODO_ODOMETRY_ADAPTIVE_RICP
+ERR_ARG, ERR_DEVICE, ERR_CAPACITY, ERR_STATE = -1, -2, -3, -4  # include/odo.h ODO_ERR_*
+
+
 class KernelForms(C.Structure):
     """odo_kernel_forms (include/odo.h): bit-identical kernel alternatives."""
     _fields_ = [("knn", C.c_int32), ("knn_split", C.c_int32), ("ransac_lanes_min_open", C.c_int32),
@@ -119,6 +137,10 @@ SIGNATURES = {
     "odo_reset": (C.c_int, [P]),
     "odo_set_latch": (C.c_int, [P, C.c_double]),
     "odo_get_latch": (C.c_double, [P]),
+    "odo_default_ricp_params": (None, [P]),
+    "odo_set_odometry": (C.c_int, [P, C.c_int, P]),
+    "odo_get_odometry": (C.c_int, [P]),
+    "odo_get_ricp": (C.c_int, [P, C.c_int, P, P, P, C.c_int]),
     "odo_track_batch": (C.c_int, [P, P, P, C.c_int, P]),
     "odo_track_batch_host": (C.c_int, [P, P, P, C.c_int, P]),
     "odo_host_alloc": (P, [C.c_size_t]),

@@ -13,7 +13,8 @@
 //   pair stream: RANSAC's rand() words (seed-only, ahead of the extraction's
 //     end), then the roll (the previous batch's last frame into slot 0), the
 //     keypoint geometry, kNN-2, matching, the DepthCovariance latch, RANSAC
-//     and PnP.
+//     and PnP (in the RANSAC / ADAPTIVE_RICP modes of odo_set_odometry the
+//     chain of run_ricp in the PnP's place).
 // So batch b+1's throughput-bound extraction overlaps batch b's latency-bound
 // pair stages, and one batch's long RANSAC / PnP overlaps the next batch's
 // pair stages on the other pair stream. One event per set ("PnP of this set
@@ -262,6 +263,23 @@ struct odo_ctx {
         void* edges = nullptr;
         uint8_t* pnp_mask = nullptr;
     } pb[NSETS];
+    // Odometry::Compute back-end of the batched path (odo_set_odometry);
+    // view_mode: the mode the last tracked batch ran in (-1: none / extraction only)
+    int odo_mode = ODO_ODOMETRY_ADAPTIVE_RBA, view_mode = -1;
+    odo_ricp_params ricp{};
+    // ADAPTIVE_RICP scratch (allocated by the first switch to the mode): one
+    // copy per pair stream, batch b uses copy b & 1 on pair stream b & 1. The
+    // batches of one stream run in order, so a copy is never shared by two
+    // batches in flight and needs no event; odo_get_ricp reads view_rb, the
+    // last batch's copy, after a full sync.
+    struct RicpBufs {
+        float *src = nullptr, *tgt = nullptr, *outp = nullptr, *guess = nullptr, *gT = nullptr;
+        double *Cs = nullptr, *Ct = nullptr, *Mah = nullptr;
+        int *is = nullptr, *it = nullptr, *offs = nullptr, *branch = nullptr, *gio = nullptr;
+        odo_ricp_result* rec = nullptr;
+    } rb[2];
+    bool ricp_alloc = false;
+    int view_rb = 0;
     // sequence state: the last tracked batch sits in frame set seq_set (its
     // last frame at slot seq_n); getters read view_set / view_n
     bool has_prev = false;
@@ -420,6 +438,30 @@ static int sync_all(odo_ctx* c) {
     return ODO_OK;
 }
 
+// ADAPTIVE_RICP scratch (odo_set_odometry): a pair's cloud has at most match_cap
+// points; sizes as launch_gicp documents them
+static void free_ricp(odo_ctx* c) {
+    for (auto& R : c->rb) {
+        void* pp[] = {R.src, R.tgt, R.outp, R.guess, R.gT, R.Cs, R.Ct, R.Mah, R.is, R.it, R.offs, R.branch, R.gio, R.rec};
+        for (void* q : pp)
+            if (q) (void)hipFree(q);
+        R = odo_ctx::RicpBufs{};
+    }
+    c->ricp_alloc = false;
+}
+static int alloc_ricp(odo_ctx* c) {
+    const size_t B = (size_t)c->maxb, N = B * c->match_cap;
+    int e;
+    for (auto& R : c->rb) {
+        if ((e = dalloc(&R.src, N * 3)) || (e = dalloc(&R.tgt, N * 3)) || (e = dalloc(&R.outp, N * 3))) return e;
+        if ((e = dalloc(&R.Cs, N * 9)) || (e = dalloc(&R.Ct, N * 9)) || (e = dalloc(&R.Mah, N * 9))) return e;
+        if ((e = dalloc(&R.is, N)) || (e = dalloc(&R.it, N))) return e;
+        if ((e = dalloc(&R.guess, B * 16)) || (e = dalloc(&R.gT, B * 16)) || (e = dalloc(&R.gio, B * 4))) return e;
+        if ((e = dalloc(&R.offs, B + 1)) || (e = dalloc(&R.branch, B)) || (e = dalloc(&R.rec, B))) return e;
+    }
+    return ODO_OK;
+}
+
 static void free_ctx(odo_ctx* c) {
     if (!c) return;
     free_hyp_session(c->hs);
@@ -443,6 +485,7 @@ static void free_ctx(odo_ctx* c) {
         for (void* q : pp)
             if (q) hipFree(q);
     }
+    free_ricp(c);
     for (int i = 0; i < c->nev; i++) hipEventDestroy(c->ev[i]);
     for (int i = 0; i < odo_ctx::KT_RING; i++) {
         if (c->kt0[i]) hipEventDestroy(c->kt0[i]);
@@ -1126,6 +1169,71 @@ int odo_reset(odo_ctx* c) {
     return reset_adaptive(c);
 }
 
+void odo_default_ricp_params(odo_ricp_params* p) {
+    if (!p) return;
+    memset(p, 0, sizeof(*p));
+    // odometry.cpp:52-53 and GeneralizedICP(10, 0.07), odometry.cpp:15
+    p->min_inliers = 20;
+    p->rmse_scale = 10.0f;
+    p->refine_at = 7.0f;
+    p->reset_at = 20.0f;
+    p->gicp_iterations = 10;
+    p->gicp_max_corr_dist = 0.07;
+}
+
+int odo_set_odometry(odo_ctx* c, int mode, const odo_ricp_params* p) {
+    // the argument checks come first and touch no device (nor the context)
+    if (mode != ODO_ODOMETRY_ADAPTIVE_RBA && mode != ODO_ODOMETRY_RANSAC && mode != ODO_ODOMETRY_ADAPTIVE_RICP)
+        return fail(ODO_ERR_ARG, "unknown odometry mode");
+    odo_ricp_params rp;
+    odo_default_ricp_params(&rp);
+    if (p) rp = *p;
+    if (rp.gicp_iterations < 1) return fail(ODO_ERR_ARG, "ricp: gicp_iterations < 1");
+    if (!(rp.gicp_max_corr_dist > 0) || !std::isfinite(rp.gicp_max_corr_dist))
+        return fail(ODO_ERR_ARG, "ricp: gicp_max_corr_dist must be positive and finite");
+    if (!std::isfinite(rp.rmse_scale) || !std::isfinite(rp.refine_at) || !std::isfinite(rp.reset_at))
+        return fail(ODO_ERR_ARG, "ricp: non-finite threshold");
+    if (!c) return fail(ODO_ERR_ARG, "null ctx");
+    // brute-force neighbour searches in one workgroup (gicp_run's limit)
+    if (mode == ODO_ODOMETRY_ADAPTIVE_RICP && c->match_cap > 16384)
+        return fail(ODO_ERR_CAPACITY, "ricp: more than 16384 points in a cloud");
+    int e;
+    if ((e = sync_all(c))) return e;
+    if (mode == ODO_ODOMETRY_ADAPTIVE_RICP && !c->ricp_alloc) {
+        if ((e = alloc_ricp(c))) {  // all or nothing: the mode stays as it was, a later switch allocates afresh
+            free_ricp(c);
+            return e;
+        }
+        c->ricp_alloc = true;
+    }
+    c->ricp = rp;
+    c->odo_mode = mode;
+    return ODO_OK;
+}
+
+int odo_get_odometry(odo_ctx* c) {
+    if (!c) return fail(ODO_ERR_ARG, "null ctx");
+    return c->odo_mode;
+}
+
+int odo_get_ricp(odo_ctx* c, int i, odo_ricp_result* r, float* src, float* tgt, int cap) {
+    if (!c || !r || cap < 0) return fail(ODO_ERR_ARG, "bad get_ricp args");
+    if (c->view_mode != ODO_ODOMETRY_ADAPTIVE_RICP) return fail(ODO_ERR_STATE, "the last batch did not run in ADAPTIVE_RICP");
+    if (i < 0 || i >= c->last_n) return fail(ODO_ERR_ARG, "bad pair index");
+    int e;
+    if ((e = sync_all(c))) return e;
+    auto& R = c->rb[c->view_rb];
+    int o[2] = {0, 0};
+    HIPCHK(hipMemcpy(r, R.rec + i, sizeof(*r), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(o, R.offs + i, sizeof(o), hipMemcpyDeviceToHost));
+    const int len = o[1] - o[0], m = std::min(len, cap);
+    if (len < 0 || o[0] < 0 || (size_t)o[1] > (size_t)c->maxb * c->match_cap)
+        return fail(ODO_ERR_STATE, "ricp: cloud offsets out of range");
+    if (src && m > 0) HIPCHK(hipMemcpy(src, R.src + 3 * (size_t)o[0], (size_t)m * 12, hipMemcpyDeviceToHost));
+    if (tgt && m > 0) HIPCHK(hipMemcpy(tgt, R.tgt + 3 * (size_t)o[0], (size_t)m * 12, hipMemcpyDeviceToHost));
+    return (src || tgt) && len > cap ? fail(ODO_ERR_CAPACITY, "cap too small") : ODO_OK;
+}
+
 int odo_set_latch(odo_ctx* c, double cov) {
     if (!c) return fail(ODO_ERR_ARG, "null ctx");
     int e;
@@ -1363,7 +1471,38 @@ int odo_extract_batch(odo_ctx* c, const uint8_t* d_bgr, const uint16_t* d_depth,
     if ((e = run_extract(c, set, d_bgr, d_depth, n, 1))) return e;
     c->view_set = set;
     c->last_n = n;
+    c->view_mode = -1;  // no pairs in view
     return ODO_OK;
+}
+
+// Odometry::Compute's RANSAC / ADAPTIVE_RICP tail (odometry.cpp:46-92) of one
+// batch, on its pair stream after launch_ransac: plan (branch, guess, cloud
+// offsets), gather (mpSourceCloud / mpTargetCloud), GICP, apply (record, Tcw,
+// inlier flags); RANSAC mode is the apply step alone. Everything the chain
+// reads (n_matches, n_good, res, T12) stays on the device: the host gives grid
+// bounds only (the batch size and match_cap).
+static void run_ricp(odo_ctx* c, hipStream_t st, int set, int n) {
+    auto& P = c->pb[set];
+    const FrameSlot f = frame_at(c, fbase(c, set));
+    const int min_inl = c->cfg.ransac.min_inlier_th;
+    if (c->odo_mode == ODO_ODOMETRY_RANSAC) {
+        launch_ricp_apply(st, P.pair_valid, P.n_matches, P.n_good, P.matches, P.good, P.best_mask, c->mask_words,
+                          c->match_cap, f.nkp, c->kp_cap, 0, P.T12, nullptr, nullptr, nullptr, nullptr, P.res, nullptr,
+                          P.pnp_mask, n);
+        return;
+    }
+    auto& R = c->rb[c->batch_counter & 1];  // the copy of this batch's pair stream
+    const odo_ricp_params& rp = c->ricp;
+    launch_ricp_plan(st, P.res, P.T12, P.pair_valid, P.n_matches, P.n_good, 20, min_inl, c->match_cap,
+                     RicpCfg{rp.min_inliers, rp.rmse_scale, rp.refine_at, rp.reset_at}, R.branch, R.guess, R.offs, n);
+    launch_ricp_gather(st, P.matches, P.n_matches, f.xyz, c->kp_cap, 0, c->match_cap, c->cfg.ransac.check_depth, R.offs,
+                       R.src, R.tgt, n);
+    GicpArgs args{R.guess, R.offs, R.offs, rp.gicp_max_corr_dist, rp.gicp_iterations, 20 /* PCL inner */};
+    launch_gicp(st, R.src, R.tgt, n, c->match_cap, c->match_cap, R.Cs, R.Ct, R.outp, R.Mah, R.is, R.it, args, R.gT,
+                R.gio);
+    launch_ricp_apply(st, P.pair_valid, P.n_matches, P.n_good, P.matches, P.good, P.best_mask, c->mask_words,
+                      c->match_cap, f.nkp, c->kp_cap, 0, P.T12, R.branch, R.offs, R.gT, R.gio, P.res, R.rec, P.pnp_mask,
+                      n);
 }
 
 // Pair stages of one batch on its pair stream `st`, over frame set `set`:
@@ -1402,9 +1541,13 @@ static int run_pairs(odo_ctx* c, hipStream_t st, int set, int n, bool latched, b
                       c->latch, P.pair_valid, 20, nullptr, c->rscr[set], P.best_mask, c->mask_words, P.res, P.T12, n,
                       c->h_open + set);
     tmark(c, 8, st);
-    if (!(c->skip & 1))
-        launch_pnp(st, P.f2_src, f.xyz, f.kun, f.ur, f.nkp, c->kp_cap, 0, c->cal, P.T12, P.pair_valid, P.n_matches, 20,
-                   P.edges, P.res, P.pnp_mask, n);
+    if (!(c->skip & 1)) {
+        if (c->odo_mode == ODO_ODOMETRY_ADAPTIVE_RBA)
+            launch_pnp(st, P.f2_src, f.xyz, f.kun, f.ur, f.nkp, c->kp_cap, 0, c->cal, P.T12, P.pair_valid, P.n_matches,
+                       20, P.edges, P.res, P.pnp_mask, n);
+        else
+            run_ricp(c, st, set, n);  // Odometry(RANSAC) / Odometry(ADAPTIVE_RICP): in place of the PnP
+    }
     tmark(c, 9, st);
     if (!defer_done) HIPCHK(hipEventRecord(c->ev_pnp_done[set], st));
     c->pdone_st[set] = st;
@@ -1569,6 +1712,8 @@ static int track_batch(odo_ctx* c, const uint8_t* d_bgr, const uint16_t* d_depth
     c->seq_n = n;
     c->view_set = s;
     c->last_n = n;
+    c->view_mode = (c->skip & 5) ? -1 : c->odo_mode;
+    c->view_rb = (int)(c->batch_counter & 1);
     c->has_prev = true;
     c->pair_counter += (uint64_t)n;
     c->batch_counter++;

@@ -318,6 +318,27 @@ struct GicpArgs {
 };
 void launch_gicp(hipStream_t st, const float* src, const float* tgt, int nprob, int max_ns, int max_nt, double* Cs,
                  double* Ct, float* outp, double* Mah, int* is, int* it, GicpArgs args, float* T12, int* outi);
+// Batched ADAPTIVE_RICP / RANSAC back-ends (k_ricp.hip), on the pair stream
+// after launch_ransac. The branch rule's constants (odometry.cpp:52-53):
+struct RicpCfg {
+    int min_inliers;
+    float rmse_scale, refine_at, reset_at;
+};
+// branch npairs, guess 16 per pair, offs npairs + 1 (source and target clouds
+// of a pair have one length: the offsets serve both)
+void launch_ricp_plan(hipStream_t st, const odo_pair_result* res, const float* T12, const int* pair_valid,
+                      const int* n_matches, const int* n_good, int min_matches, int min_inlier_th, int match_cap,
+                      RicpCfg cfg, int* branch, float* guess, int* offs, int npairs);
+// src / tgt: up to npairs * match_cap points
+void launch_ricp_gather(hipStream_t st, const odo_dmatch* matches, const int* n_matches, const float* xyz, int kp_cap,
+                        int slot0, int match_cap, int check_depth, const int* offs, float* src, float* tgt,
+                        int npairs);
+// RANSAC mode: branch, offs, gT, gio and ricp null (every pair keeps RANSAC's T12)
+void launch_ricp_apply(hipStream_t st, const int* pair_valid, const int* n_matches, const int* n_good,
+                       const odo_dmatch* matches, const void* good, const uint32_t* best_mask, int mask_words,
+                       int match_cap, const int* nkp, int kp_cap, int slot0, const float* T12, const int* branch,
+                       const int* offs, const float* gT, const int* gio, odo_pair_result* res, odo_ricp_result* ricp,
+                       uint8_t* inlier_mask, int npairs);
 // PnPRansac (k_pnpransac.hip), nprob problems, problem p = points [offs[p], offs[p+1]):
 // idx P*H*5, model P*H*6, Rproj P*H*9, mask H*sum(n), good P*H, state P*4, res P, mask_out sum(n)
 int pnp_ransac_max_points();

@@ -160,6 +160,55 @@ int odo_host_free(void* p);
 int odo_extract_batch(odo_ctx* ctx, const uint8_t* d_bgr, const uint16_t* d_depth, int n);
 int odo_synchronize(odo_ctx* ctx);
 
+/* ---- Odometry::Compute back-end of the batched path (odometry.cpp:43-117).
+ * Every odo_track_batch* entry point (device, host, sparse-depth, async) runs
+ * the context's mode:
+ *   ADAPTIVE_RBA   Ransac::Iterate + PnPSolver::Compute (odometry.cpp:105-116),
+ *                  the default.
+ *   RANSAC         Ransac::Iterate alone (odometry.cpp:81-92).
+ *   ADAPTIVE_RICP  Ransac::Iterate, then when mvInliers.size() < min_inliers or
+ *                  rmse * rmse_scale >= refine_at (odometry.cpp:52, evaluated in
+ *                  float as there) GeneralizedICP::Compute on Ransac's
+ *                  mpSourceCloud / mpTargetCloud (ransac.cpp:161-189: the
+ *                  depth-valid matches in KnnMatch order), from the identity
+ *                  when rmse * rmse_scale >= reset_at (odometry.cpp:53-58;
+ *                  T12 = identity if GICP does not converge), else from
+ *                  Ransac::mT12 (odometry.cpp:60-65; Ransac::mT12 if it does
+ *                  not). Decision, clouds, GICP and the pose stay on the
+ *                  device: a batch gains no host synchronisation.
+ * In RANSAC and ADAPTIVE_RICP odo_pair_result.T12, rmse, n_good, n_inliers,
+ * ransac_ok, visited, n_sweeps and n_fit_points are what ADAPTIVE_RBA reports;
+ * Tcw is the pose Odometry::Compute sets (the chosen T12 times F1's pose, the
+ * identity in the batched contract; odometry.cpp:70-72, 85-87), so
+ * odo_chain_poses and the trajectory writer apply unchanged; PnP does not
+ * run; the mask odo_get_pair returns as pnp_inliers holds F2's inlier flags,
+ * SetInlier(m.trainIdx) for every m of mvInliers (odometry.cpp:75-76, 90-91),
+ * and odo_pair_result.pnp_inliers is the number of flags set. A pair without a
+ * predecessor reports what ADAPTIVE_RBA reports for it. */
+#define ODO_ODOMETRY_ADAPTIVE_RBA  0   /* default */
+#define ODO_ODOMETRY_RANSAC        1   /* odometry.cpp:81-92 */
+#define ODO_ODOMETRY_ADAPTIVE_RICP 2   /* odometry.cpp:46-78 */
+/* The reference's constants: 20, 10.f, 7.f, 20.f, GeneralizedICP(10, 0.07)
+ * (odometry.cpp:15, 52-53). */
+void odo_default_ricp_params(odo_ricp_params* p);
+/* Select the mode, from the next batch on; p: ADAPTIVE_RICP's constants (NULL =
+ * the defaults; ignored by the other modes). Synchronises the context's
+ * streams. ODO_ERR_ARG: unknown mode, gicp_iterations < 1, gicp_max_corr_dist
+ * <= 0 (or not finite), a non-finite rmse_scale / refine_at / reset_at.
+ * ODO_ERR_CAPACITY: ADAPTIVE_RICP on a context whose keypoint capacity exceeds
+ * GICP's 16384 points per cloud. The sequence state (previous frame, latch,
+ * pair counter, ADAPTIVE thresholds) is kept, and odo_reset keeps the mode. The
+ * GICP scratch is allocated by the first switch to ADAPTIVE_RICP; a context
+ * left in the default mode allocates and launches nothing for this. */
+int odo_set_odometry(odo_ctx* ctx, int mode, const odo_ricp_params* p);
+int odo_get_odometry(odo_ctx* ctx);   /* ODO_ODOMETRY_*, < 0 on error */
+/* Pair i of the last batch when it ran in ADAPTIVE_RICP (else ODO_ERR_STATE):
+ * the record and, optionally, the pair's mpSourceCloud / mpTargetCloud (src /
+ * tgt: cap points of 3 floats each, r->n_cloud written; more than cap points:
+ * ODO_ERR_CAPACITY after copying cap). The clouds of a pair on branch 0 are
+ * not built (n_cloud = 0). Synchronises. */
+int odo_get_ricp(odo_ctx* ctx, int i, odo_ricp_result* r, float* src, float* tgt, int cap);
+
 /* Read back frame features of batch slot i (0 <= i < n of the last call). */
 int odo_get_frame(odo_ctx* ctx, int i, orb_kp* kps, uint8_t* desc, float* kps_un, float* xyz,
                   float* u_right, int cap, int* n);

@@ -145,6 +145,26 @@ typedef struct odo_pair_result {
     int32_t n_fit_points; /* points added to TransformationFromCorrespondences fits (F of SURVEY §8(d)) */
 } odo_pair_result;
 
+/* The constants of Odometry::Compute's ADAPTIVE_RICP branch rule and of its
+ * GeneralizedICP (odometry.cpp:15, 52-53) made explicit; odo_set_odometry. */
+typedef struct odo_ricp_params {
+    int32_t min_inliers;        /* 20   : mvInliers.size() < 20                     */
+    float   rmse_scale;         /* 10.f : rmse * 10.0f                              */
+    float   refine_at;          /* 7.f  : >= -> GICP                                */
+    float   reset_at;           /* 20.f : >= -> GICP from identity, else from mT12  */
+    int32_t gicp_iterations;    /* 10   : GeneralizedICP(10, 0.07)                  */
+    double  gicp_max_corr_dist; /* 0.07                                             */
+} odo_ricp_params;
+
+/* What ADAPTIVE_RICP did for one pair of the last batch (odo_get_ricp). 96 bytes. */
+typedef struct odo_ricp_result {
+    float   T12[16];     /* GeneralizedICP::mT12 when GICP ran for the pair, identity otherwise */
+    int32_t branch;      /* 0 keep RANSAC's mT12, 1 GICP from identity, 2 GICP from mT12 */
+    int32_t converged, iterations, n_corr;   /* as odo_gicp; 0 when GICP did not run */
+    int32_t n_cloud;     /* points in mpSourceCloud (= mpTargetCloud) */
+    int32_t pad[3];
+} odo_ricp_result;
+
 #ifdef __cplusplus
 }
 #endif

@@ -543,7 +543,9 @@ __global__ void __launch_bounds__(FS_TH) k_fast_seg(const uint8_t* __restrict__ 
 // DistributeOctTree as a parallel restatement: the std::list is an array in
 // list order rebuilt every pass with scans; push_front order, creation order
 // (the pinned tie-break for the (size, pointer) sort) and "first max wins"
-// are reproduced exactly.
+// are reproduced exactly. The first iterations of phase 1
+// (at most four) take their key counts from one histogram of the keys' path
+// codes instead of two passes over the keys each (ot_tree).
 struct ONode {
     int16_t x0, y0, x1, y1;
     int32_t cnt;
@@ -569,6 +571,25 @@ struct ONode {
 #endif
 #ifndef OT_RANK_MAX
 #define OT_RANK_MAX 512  // phase 2's node ranks counted (not sorted) up to this many entries
+#endif
+#ifdef ODO_OCTREE_PROFILE
+// -DODO_OCTREE_PROFILE: the device wall clock (10 ns ticks) of frame 0's first-
+// and last-level workgroups where their stages end (S start, G gather, I
+// initial nodes, 1 / 2 an iteration of that phase, R retention), printed by
+// thread 0 when the workgroup is done (tools/octree_probe.py). s_vars[8] is
+// the number of stamps taken, -1 in every other workgroup.
+#define OT_NSTAMP 48
+__device__ unsigned long long g_ot_stamp[2][OT_NSTAMP];
+#define OT_STAMP(tag)                                                                                   \
+    do {                                                                                                \
+        if (threadIdx.x == 0 && s_vars[8] >= 0 && s_vars[8] < OT_NSTAMP)                                \
+            g_ot_stamp[s_vars[9]][s_vars[8]++] = ((unsigned long long)(tag) << 56) | (wall_clock64() & 0xFFFFFFFFFFFFFFull); \
+    } while (0)
+#else
+#define OT_STAMP(tag) ((void)0)
+#endif
+#ifndef OT_HIST_WAVE0
+#define OT_HIST_WAVE0 1  // lists of at most 64 nodes in wave 0 alone (0: the A/B build without)
 #endif
 enum { OT_LDK = 1, OT_LDN = 2 };
 template <bool RES, int LD, typename F>
@@ -691,7 +712,8 @@ ODO_INLINE int2 block_exclusive_scan2(int a, int b, int* tmp, int2* total) {
 // The tree over the n > 0 gathered keys of one (frame, level) and the best key
 // of every final node to out[]. The keys are in rk[] (RES, see ot_pass) or in
 // keys[]; a key's node is its position in the current list, with the quadrant
-// it falls into (bits 16-17) between an iteration's classify and remap passes.
+// it falls into (bits 16-17) between an iteration's classify and remap passes
+// (and its path code between the histogram's classify and lookup passes).
 template <bool RES>
 ODO_INLINE void ot_tree(const int n, const LevelDesc& L, char* smem, int* s_vars, const int node_cap,
                         uint32_t (&rk)[OT_KB], int (&rn)[OT_KB], const uint32_t* keys, int32_t* knode,
@@ -718,61 +740,317 @@ ODO_INLINE void ot_tree(const int n, const LevelDesc& L, char* smem, int* s_vars
     const int nIni = (int)roundf((float)(maxX - minX) / (float)(maxY - minY));
     const float hX = (float)(maxX - minX) / (float)nIni;
 
-    // ---- initial nodes
-    for (int i = t; i < nIni; i += OT_THREADS) {
-        ONode nd;
-        nd.x0 = (int16_t)(int)(hX * (float)i);
-        nd.x1 = (int16_t)(int)(hX * (float)(i + 1));
-        nd.y0 = 0;
-        nd.y1 = (int16_t)(maxY - minY);
-        nd.cnt = 0;
-        nd.seq = i;
-        nodesA[i] = nd;
+    if (nIni < 1) {  // uniform: no root node, nothing retained
+        if (t == 0) *ocnt_fl = 0;
+        return;
     }
+    // ---- phase 1 down to depth D from one histogram. While every node with
+    // more than one key is divided, a child's box depends on its parent's box
+    // alone, so a key's quadrant path through the first D levels follows from
+    // its own (x, y) and the count of every node down to depth D is a sum over
+    // the histogram of depth-D path codes (root index, then two bits per
+    // level). The keys are passed over twice (codes and histogram; node
+    // lookup) however many of the D iterations run; the list bookkeeping of
+    // an iteration (scans, push-front order, seq, sorted-list entries, exits)
+    // reads its child counts from the pyramid and is over nodes only.
+    // A node of depth d and path p is entry p of level d; levels are stored
+    // one after the other (level d at nIni (4^d - 1) / 3) and a node carries
+    // that index as its tag. D: the deepest level that fits node_cap entries.
+    int D = 0;
+    while (D < 4 && (nIni << (2 * D + 2)) <= node_cap) D++;
+    const int offD = nIni * ((1 << (2 * D)) - 1) / 3;   // level D
+    const int nT = offD + (nIni << (2 * D));             // all levels: < 4/3 node_cap
+    int* hist = cc;                                       // [nT] key counts
+    int* postab = cc + nT;                                // [nT] list position at the stop
+    uint16_t* tagA = reinterpret_cast<uint16_t*>(cc + 3 * node_cap);  // [node_cap] tags of nodesA
+    uint16_t* tagB = tagA + node_cap;                                 // [node_cap] tags of nodesB
+    for (int i = t; i < nT; i += OT_THREADS) hist[i] = 0;
     __syncthreads();
-    // the initial nodes' key counts: nIni is 1-2 for 4:3 frames, so every
-    // key's atomic hit the same one or two LDS words (a 64-way serialised
-    // atomic per key batch); the first four nodes are counted in registers
-    // and added once per thread (the same integer counts)
-    int ic0 = 0, ic1 = 0, ic2 = 0, ic3 = 0;
-    ot_pass<RES, OT_LDK>(
-        n, t, rk, rn, keys, knode, [&](int k, uint32_t key, int& node) {
-            const float x = (float)(key & 0xfff);
-            const int ni = (int)(x / hX);
-            node = ni;
-            ic0 += ni == 0;
-            ic1 += ni == 1;
-            ic2 += ni == 2;
-            ic3 += ni == 3;
-            if (ni > 3) atomicAdd(&nodesA[ni].cnt, 1);
-        });
-    if (ic0) atomicAdd(&nodesA[0].cnt, ic0);
-    if (ic1) atomicAdd(&nodesA[1].cnt, ic1);
-    if (ic2) atomicAdd(&nodesA[2].cnt, ic2);
-    if (ic3) atomicAdd(&nodesA[3].cnt, ic3);
-    __syncthreads();
-    // erase empty initial nodes (keep order)
-    if (t == 0) {
-        int w = 0;
-        for (int i = 0; i < nIni; i++) {
-            iscr[i] = -1;
-            if (nodesA[i].cnt > 0) {
-                iscr[i] = w;
-                nodesB[w++] = nodesA[i];
-            }
+    ot_pass<RES, OT_LDK>(n, t, rk, rn, keys, knode, [&](int k, uint32_t key, int& node) {
+        const int x = key & 0xfff, y = (key >> 12) & 0xfff;
+        const int ni = min((int)((float)x / hX), nIni - 1);
+        int x0 = (int)(hX * (float)ni), x1 = (int)(hX * (float)(ni + 1)), y0 = 0, y1 = maxY - minY;
+        int code = ni;
+        for (int d = 0; d < D; d++) {
+            const int mx = x0 + ((x1 - x0 + 1) >> 1), my = y0 + ((y1 - y0 + 1) >> 1);  // DivideNode's ceil halves
+            const bool right = x >= mx, low = y >= my;
+            x0 = right ? mx : x0;
+            x1 = right ? x1 : mx;
+            y0 = low ? my : y0;
+            y1 = low ? y1 : my;
+            code = code * 4 + (right ? 1 : 0) + (low ? 2 : 0);
         }
-        s_size = w;
-        s_seq = nIni;
-        s_finish = 0;
-        s_phase = 1;
+        atomicAdd(&hist[offD + code], 1);
+        node = code;
+    });
+    __syncthreads();
+    OT_STAMP('H');
+    // the levels above: level D - 1 by every thread, the rest (at most
+    // node_cap / 16 entries each) and the root list by wave 0 alone
+    if (D > 0) {
+        const int w = nIni << (2 * D - 2), o = offD - w;
+        for (int j = t; j < w; j += OT_THREADS) {
+            const int* h = hist + offD + 4 * j;
+            hist[o + j] = h[0] + h[1] + h[2] + h[3];
+        }
     }
     __syncthreads();
-    ot_pass<RES, OT_LDN>(n, t, rk, rn, keys, knode, [&](int k, uint32_t key, int& node) { node = iscr[node]; });
-    for (int i = t; i < s_size; i += OT_THREADS) nodesA[i] = nodesB[i];
+    if (t < 64) {
+        int o1 = offD - (D > 0 ? nIni << (2 * D - 2) : 0);  // level d + 1
+        for (int d = D - 2; d >= 0; d--) {
+            const int w = nIni << (2 * d), o = o1 - w;
+            for (int j = t; j < w; j += 64) {
+                const int* h = hist + o1 + 4 * j;
+                hist[o + j] = h[0] + h[1] + h[2] + h[3];
+            }
+            o1 = o;
+            wave_lds_sync();
+        }
+        // the initial nodes that hold keys, in order
+        if (t == 0) {
+            int w = 0;
+            for (int i = 0; i < nIni; i++) {
+                const int c = hist[i];
+                if (c > 0) {
+                    ONode nd;
+                    nd.x0 = (int16_t)(int)(hX * (float)i);
+                    nd.x1 = (int16_t)(int)(hX * (float)(i + 1));
+                    nd.y0 = 0;
+                    nd.y1 = (int16_t)(maxY - minY);
+                    nd.cnt = c;
+                    nd.seq = i;
+                    nodesA[w] = nd;
+                    tagA[w] = (uint16_t)i;
+                    w++;
+                }
+            }
+            s_size = w;
+            s_seq = nIni;
+            s_finish = 0;
+            s_phase = 1;
+        }
+    }
     __syncthreads();
+    OT_STAMP('I');
 
     ONode* cur = nodesA;
     ONode* nxt = nodesB;
+    {
+        uint16_t* ctag = tagA;
+        uint16_t* ntag = tagB;
+        int d = 0, od = 0;  // the list's depth and its level's offset
+#if OT_HIST_WAVE0
+        // While the list has at most 64 nodes (depths 0-2 of one root node,
+        // and depth 3 if none of its 64 nodes is empty) wave 0 runs the
+        // iterations alone, a node per lane: wave scans, no workgroup
+        // barrier, the list's state in registers. The other waves wait.
+        if (t < 64) {
+            int S = s_size, seq = s_seq, prevS = S, vc = 0, fin = 0, ph = 1;
+            while (d < D && S <= 64) {
+                const int oc = od + (nIni << (2 * d));  // level d + 1
+                ONode P0;
+                int tag = 0, e = 0, ne = 0, s = 0, hc[4] = {0, 0, 0, 0};
+                if (t < S) {
+                    P0 = cur[t];
+                    tag = ctag[t];
+                    if (P0.cnt > 1) {
+#pragma unroll
+                        for (int q = 0; q < 4; q++) {
+                            hc[q] = hist[oc + 4 * (tag - od) + q];
+                            e += hc[q] > 0;
+                            ne += hc[q] > 1;
+                        }
+                    } else s = 1;
+                }
+                const int v = e | (ne << 16);
+                const int xv = wave_incl_scan(v), xs = wave_incl_scan(s);
+                const int tv = __builtin_amdgcn_readlane(xv, 63), ts = __builtin_amdgcn_readlane(xs, 63);
+                const int totalChildren = tv & 0xFFFF, expBase = tv >> 16, newSize = totalChildren + ts;
+                const int ex_e = (xv - v) & 0xFFFF, ex_ne = (xv - v) >> 16, ex_s = xs - s;
+                if (t < S) {
+                    if (s) {
+                        const int pos = totalChildren + ex_s;
+                        nxt[pos] = P0;
+                        ntag[pos] = (uint16_t)tag;
+                    } else {
+                        const int blockStart = totalChildren - (ex_e + e);
+                        const int hx = (P0.x1 - P0.x0 + 1) >> 1, hy = (P0.y1 - P0.y0 + 1) >> 1;
+                        const int ctag0 = oc + 4 * (tag - od);
+                        int r = 0, vi = ex_ne;
+#pragma unroll
+                        for (int q = 0; q < 4; q++) {
+                            const int c = hc[q];
+                            if (c > 0) {
+                                ONode C;
+                                const int qx = q & 1, qy = q >> 1;
+                                C.x0 = (int16_t)(qx ? P0.x0 + hx : P0.x0);
+                                C.x1 = (int16_t)(qx ? P0.x1 : P0.x0 + hx);
+                                C.y0 = (int16_t)(qy ? P0.y0 + hy : P0.y0);
+                                C.y1 = (int16_t)(qy ? P0.y1 : P0.y0 + hy);
+                                C.cnt = c;
+                                C.seq = seq + ex_e + r;
+                                const int pos = blockStart + (e - 1 - r);
+                                nxt[pos] = C;
+                                ntag[pos] = (uint16_t)(ctag0 + q);
+                                if (c > 1) sortk[vi++] = ot_key(c, C.seq, pos);
+                                r++;
+                            }
+                        }
+                    }
+                }
+                prevS = S;
+                S = newSize;
+                seq += totalChildren;
+                vc = expBase;
+                ONode* tmpp = cur;
+                cur = nxt;
+                nxt = tmpp;
+                uint16_t* tmpt = ctag;
+                ctag = ntag;
+                ntag = tmpt;
+                od = oc;
+                d++;
+                wave_lds_sync();  // the new list, read by other lanes in the next iteration
+                OT_STAMP('1');
+                if (newSize >= N || newSize == prevS) fin = 1;
+                else if (newSize + expBase * 3 > N) ph = 2;
+                if (fin || ph == 2) break;
+            }
+            if (t == 0) {
+                if (d > 0) {
+                    s_prev = prevS;
+                    s_size = S;
+                    s_seq = seq;
+                    s_vcnt = vc;
+                    s_finish = fin;
+                    s_phase = ph;
+                }
+                s_J = d;
+            }
+        }
+        __syncthreads();
+        d = s_J;  // the list wave 0 left: nodesA / tagA at even depths
+        od = nIni * ((1 << (2 * d)) - 1) / 3;
+        cur = (d & 1) ? nodesB : nodesA;
+        nxt = (d & 1) ? nodesA : nodesB;
+        ctag = (d & 1) ? tagB : tagA;
+        ntag = (d & 1) ? tagA : tagB;
+#endif
+        while (d < D && !s_finish && s_phase == 1) {
+            // one phase-1 iteration (the loop below, which see) without its key passes
+            const int S = s_size, seq0 = s_seq;  // S > 0: at least one barrier before thread 0 replaces them
+            const int oc = od + (nIni << (2 * d));  // level d + 1
+            int childBase = 0, survBase = 0, expBase = 0;
+            for (int cb = 0; cb < S; cb += OT_THREADS) {
+                const int i = cb + t;
+                int e = 0, ne = 0, s = 0;
+                if (i < S) {
+                    if (cur[i].cnt > 1) {
+                        const int* h = hist + oc + 4 * (ctag[i] - od);
+#pragma unroll
+                        for (int q = 0; q < 4; q++) {
+                            e += h[q] > 0;
+                            ne += h[q] > 1;
+                        }
+                    } else s = 1;
+                }
+                int2 tp;
+                const int2 ex = block_exclusive_scan2(e | (ne << 16), s, scan, &tp);
+                if (i < S) {  // read back below by the same thread
+                    iscr[i] = childBase + (ex.x & 0xFFFF);
+                    npos[i * 4 + 0] = e;
+                    npos[i * 4 + 1] = (ex.x >> 16) + expBase;
+                    npos[i * 4 + 2] = survBase + ex.y;
+                    npos[i * 4 + 3] = s;
+                }
+                childBase += tp.x & 0xFFFF;
+                expBase += tp.x >> 16;
+                survBase += tp.y;
+            }
+            const int totalChildren = childBase;
+            const int newSize = totalChildren + survBase;
+            for (int i = t; i < S; i += OT_THREADS) {
+                const ONode P0 = cur[i];
+                const int tag = ctag[i];
+                const int e = npos[i * 4 + 0];
+                if (npos[i * 4 + 3]) {
+                    const int pos = totalChildren + npos[i * 4 + 2];
+                    nxt[pos] = P0;
+                    ntag[pos] = (uint16_t)tag;
+                } else {
+                    const int blockStart = totalChildren - (iscr[i] + e);
+                    const int hx = (P0.x1 - P0.x0 + 1) >> 1, hy = (P0.y1 - P0.y0 + 1) >> 1;
+                    const int ctag0 = oc + 4 * (tag - od);
+                    int r = 0, v = npos[i * 4 + 1];
+#pragma unroll
+                    for (int q = 0; q < 4; q++) {
+                        const int c = hist[ctag0 + q];
+                        if (c > 0) {
+                            ONode C;
+                            const int qx = q & 1, qy = q >> 1;
+                            C.x0 = (int16_t)(qx ? P0.x0 + hx : P0.x0);
+                            C.x1 = (int16_t)(qx ? P0.x1 : P0.x0 + hx);
+                            C.y0 = (int16_t)(qy ? P0.y0 + hy : P0.y0);
+                            C.y1 = (int16_t)(qy ? P0.y1 : P0.y0 + hy);
+                            C.cnt = c;
+                            C.seq = seq0 + iscr[i] + r;
+                            const int pos = blockStart + (e - 1 - r);
+                            nxt[pos] = C;
+                            ntag[pos] = (uint16_t)(ctag0 + q);
+                            if (c > 1) {
+                                sortk[v] = ot_key(c, C.seq, pos);
+                                v++;
+                            }
+                            r++;
+                        }
+                    }
+                }
+            }
+            if (t == 0) {
+                s_prev = S;
+                s_size = newSize;
+                s_seq = seq0 + totalChildren;
+                s_vcnt = expBase;
+                if (newSize >= N || newSize == S) s_finish = 1;
+                else if (newSize + expBase * 3 > N) s_phase = 2;
+            }
+            ONode* tmpp = cur;
+            cur = nxt;
+            nxt = tmpp;
+            uint16_t* tmpt = ctag;
+            ctag = ntag;
+            ntag = tmpt;
+            od = oc;
+            d++;
+            __syncthreads();
+            OT_STAMP('1');
+        }
+        // where the restated iterations stop (d = 0: at the initial nodes),
+        // every node of the list enters its position under its tag and a key
+        // finds its node at the first level of its path that holds one key,
+        // or at level d
+        const int S = s_size;
+        for (int i = t; i < S; i += OT_THREADS) postab[ctag[i]] = i;
+        __syncthreads();
+        ot_pass<RES, OT_LDN>(n, t, rk, rn, keys, knode, [&](int k, uint32_t key, int& node) {
+            // the counts along the path are read together (d <= D <= 4), not
+            // one after the other: two LDS round trips per key, not d + 2
+            const int code = node;
+            int idx[5], c[5], o = 0;
+#pragma unroll
+            for (int dd = 0; dd < 5; dd++) {
+                idx[dd] = o + (code >> (2 * max(D - dd, 0)));
+                o += nIni << (2 * dd);
+                c[dd] = dd < d ? hist[idx[dd]] : 1;
+            }
+            int sel = idx[4];
+#pragma unroll
+            for (int dd = 3; dd >= 0; dd--) sel = c[dd] == 1 ? idx[dd] : sel;
+            node = postab[sel];
+        });
+        __syncthreads();  // the tables' room is the loop's cc
+        OT_STAMP('L');
+    }
     // vSizeAndPtr entries live in sortk as (cnt<<32 | seq); positions resolved by seq lookup
     int vcount = 0;
 
@@ -890,6 +1168,7 @@ ODO_INLINE void ot_tree(const int n, const LevelDesc& L, char* smem, int* s_vars
                 else if (newSize + expBase * 3 > N) s_phase = 2;
             }
             vcount = expBase;
+            OT_STAMP('1');
             ONode* tmpp = cur;
             cur = nxt;
             nxt = tmpp;
@@ -1067,6 +1346,7 @@ ODO_INLINE void ot_tree(const int n, const LevelDesc& L, char* smem, int* s_vars
                 const int i = node & 0xFFFF;
                 node = cc[i * 4 + (iscr[i] < 0 ? 0 : node >> 16)];
             });
+            OT_STAMP('2');
             ONode* tmpp = cur;
             cur = nxt;
             nxt = tmpp;
@@ -1088,6 +1368,7 @@ ODO_INLINE void ot_tree(const int n, const LevelDesc& L, char* smem, int* s_vars
         if (node < cap && best[node] == (((key >> 24) << 23) | (0x7FFFFFu - (unsigned)k))) out[node] = key;
     });
     if (t == 0) *ocnt_fl = S < cap ? S : cap;
+    OT_STAMP('R');
 }
 
 __global__ void __launch_bounds__(OT_THREADS) k_octree(const uint32_t* __restrict__ cand,
@@ -1124,10 +1405,18 @@ __global__ void __launch_bounds__(OT_THREADS) k_octree(const uint32_t* __restric
     const int res_cap = min(OT_THREADS * OT_KB, 16 * node_cap);
     uint32_t rk[OT_KB];
     int rn[OT_KB];
+#ifdef ODO_OCTREE_PROFILE
+    if (t == 0) {
+        s_vars[8] = f == 0 && (l == 0 || l == nlevels - 1) ? 0 : -1;
+        s_vars[9] = l != 0;
+    }
+    OT_STAMP('S');
+#endif
 
     // ---- gather candidates of this level's cells in cell order
     const int n = ot_gather(cand, cand_cnt, cell0, nc, cell_cap, stage, res_cap, scan);
     __syncthreads();
+    OT_STAMP('G');
     if (n == 0) {
         if (t == 0) *ocnt_fl = 0;
         return;
@@ -1146,6 +1435,14 @@ __global__ void __launch_bounds__(OT_THREADS) k_octree(const uint32_t* __restric
         ot_tree<false>(n, L, smem, s_vars, node_cap, rk, rn, keys_g + kbase, knode_g + kbase, out, ocnt_fl,
                        okp_stride);
     }
+#ifdef ODO_OCTREE_PROFILE
+    if (t == 0 && s_vars[8] > 0) {
+        const unsigned long long* st = g_ot_stamp[s_vars[9]];
+        for (int i = 1; i < s_vars[8]; i++)
+            printf("OTP level %d keys %d stamp %d %c %llu\n", l, n, i, (int)(st[i] >> 56),
+                   (st[i] - st[i - 1]) & 0xFFFFFFFFFFFFFFull);
+    }
+#endif
 }
 
 // ============================================================ blur

@@ -15,7 +15,8 @@ from . import _abi
 from ._abi import (DETECTOR_ADAPTIVE_FAST, DETECTOR_ADAPTIVE_ORB, DETECTOR_ORB_SLAM2, KNN_FORM_FP4, KNN_FORM_VALU,
                    PYRAMID_FORM_AUTO, PYRAMID_FORM_CHAIN, PYRAMID_FORM_FUSED, PYRAMID_FORM_FUSED_NOBLUR,
                    AdaptiveParams, Calib, Config, DMatch, PnPRansacResult,
-                   DMATCH_DTYPE, KP_DTYPE, OrbParams, PAIR_DTYPE, PairResult, RansacParams, Rng, check, load, ptr,
+                   DMATCH_DTYPE, KP_DTYPE, LANDMARK_DTYPE, LOCAL_MAP_DTYPE, LM_BAD, LM_HAS_OBS, LM_SEEN, LocalMapResult,
+                   OrbParams, PAIR_DTYPE, PairResult, RansacParams, Rng, check, load, ptr,
                    ODOMETRY_ADAPTIVE_RBA, ODOMETRY_ADAPTIVE_RICP, ODOMETRY_RANSAC, RicpParams, RicpResult)
 
 __all__ = ["Odometry", "HostFrames", "PinnedResults", "default_config", "load", "KP_DTYPE", "DMATCH_DTYPE", "PAIR_DTYPE", "rng_stream",
@@ -23,7 +24,8 @@ __all__ = ["Odometry", "HostFrames", "PinnedResults", "default_config", "load", 
            "DETECTOR_ADAPTIVE_FAST", "DETECTOR_ADAPTIVE_ORB", "KNN_FORM_FP4", "KNN_FORM_VALU",
            "PYRAMID_FORM_AUTO", "PYRAMID_FORM_FUSED", "PYRAMID_FORM_CHAIN",
            "PYRAMID_FORM_FUSED_NOBLUR", "ODOMETRY_ADAPTIVE_RBA", "ODOMETRY_RANSAC", "ODOMETRY_ADAPTIVE_RICP",
-           "RicpParams", "RicpResult", "default_ricp_params"]
+           "RicpParams", "RicpResult", "default_ricp_params", "LANDMARK_DTYPE", "LOCAL_MAP_DTYPE", "LocalMapResult",
+           "LM_BAD", "LM_SEEN", "LM_HAS_OBS"]
 
 
 def default_config(width=640, height=480, max_batch=1, nfeatures=1000, iterations=200, seed=0x5EED0000,
@@ -347,6 +349,61 @@ class Odometry:
                                     ptr(pin), ptr(src)))
         return dict(matches=matches[:nm.value], good=good[:ng.value], ransac_inliers=rin[:ng.value],
                     pnp_inliers=pin, f2_src=src)
+
+    def kp_capacity(self) -> int:
+        """odo_kp_capacity: keypoint slots per frame (the row length of a prior)."""
+        r = self.lib.odo_kp_capacity(self.h)
+        if r < 0:
+            check(r)
+        return r
+
+    def track_local_map(self, lms, Tcw, prior=None, th: float = 8.0, nn_ratio: float = 0.8):
+        """odo_track_local_map: Tracking::TrackLocalMap (tracking.cpp:231-261) for
+        every frame of the last batch, on the device. lms: LANDMARK_DTYPE array;
+        Tcw: n x 4 x 4 poses (world -> camera), one per frame of the batch;
+        prior: n rows of slot -> landmark index (-1 empty; rows shorter than the
+        keypoint capacity are padded with -1) or None. Every frame starts from
+        its own pose: a refined pose does not feed the next frame. Returns a
+        LOCAL_MAP_DTYPE array of n records."""
+        lms = np.ascontiguousarray(lms, LANDMARK_DTYPE)
+        T = np.ascontiguousarray(Tcw, np.float32).reshape(-1, 16)
+        n, kc = T.shape[0], self.kp_capacity()
+        pr = None
+        if prior is not None:
+            pr = np.full((n, kc), -1, np.int32)
+            if len(prior) != n:
+                raise ValueError(f"prior has {len(prior)} rows for {n} poses")
+            for i, row in enumerate(prior):
+                row = np.asarray(row, np.int32)
+                if row.size > kc:
+                    raise ValueError(f"prior row {i} has {row.size} slots, the context {kc}")
+                pr[i, :row.size] = row
+        out = np.zeros(n, LOCAL_MAP_DTYPE)
+        self._lm_n = None
+        check(self.lib.odo_track_local_map(self.h, ptr(lms), len(lms), ptr(T), ptr(pr), kc, th, nn_ratio, ptr(out)))
+        self._lm_n = len(lms)
+        return out
+
+    def local_map(self, i: int):
+        """odo_get_local_map: frame i of the last track_local_map. Returns
+        dict(slot_lm nkp, proj n_lms x 3 (NaN: not in view), pnp_outlier nkp)."""
+        if getattr(self, "_lm_n", None) is None:
+            raise RuntimeError("local_map: no track_local_map call on this context")
+        kc = self.kp_capacity()
+        sl = np.full(kc, -1, np.int32)
+        out = np.zeros(kc, np.uint8)
+        proj = np.zeros((self._lm_n, 3), np.float32)
+        m = self.frame_count(i)
+        check(self.lib.odo_get_local_map(self.h, i, ptr(sl), ptr(proj), ptr(out), kc))
+        return dict(slot_lm=sl[:m], proj=proj, pnp_outlier=out[:m])
+
+    def frame_count(self, i: int) -> int:
+        """Keypoints of frame i of the last batch."""
+        n = C.c_int(0)
+        rc = self.lib.odo_get_frame(self.h, i, None, None, None, None, None, 0, C.byref(n))
+        if rc != 0 and rc != _abi.ERR_CAPACITY:
+            check(rc)
+        return n.value
 
     def debug_pyramid(self, i: int, total: int):
         out = np.zeros(total + 4096, np.uint8)

@@ -79,6 +79,12 @@ class RicpResult(C.Structure):
                 ("iterations", C.c_int32), ("n_corr", C.c_int32), ("n_cloud", C.c_int32), ("pad", C.c_int32 * 3)]
 
 
+class LocalMapResult(C.Structure):
+    """odo_local_map_result (include/odo_types.h)."""
+    _fields_ = [("Tcw", C.c_float * 16), ("n_in_view", C.c_int32), ("n_matches", C.c_int32), ("n_edges", C.c_int32),
+                ("pnp_inliers", C.c_int32), ("n_map_inliers", C.c_int32), ("pad", C.c_int32 * 3)]
+
+
 ODOMETRY_ADAPTIVE_RBA = 0   # include/odo.h ODO_ODOMETRY_ADAPTIVE_RBA
 ODOMETRY_RANSAC = 1         # include/odo.h ODO_ODOMETRY_RANSAC
 ODOMETRY_ADAPTIVE_RICP = 2  # include/odo.h ODO_ODOMETRY_ADAPTIVE_RICP
@@ -125,6 +131,8 @@ DMATCH_DTYPE = np.dtype([("queryIdx", "<i4"), ("trainIdx", "<i4"), ("imgIdx", "<
 PAIR_DTYPE = np.dtype([("T12", "<f4", 16), ("Tcw", "<f4", 16), ("rmse", "<f4"), ("n_matches", "<i4"),
                        ("n_good", "<i4"), ("n_inliers", "<i4"), ("ransac_ok", "<i4"), ("pnp_inliers", "<i4"),
                        ("visited", "<i4"), ("n_queries", "<i4"), ("n_sweeps", "<i4"), ("n_fit_points", "<i4")])
+LOCAL_MAP_DTYPE = np.dtype([("Tcw", "<f4", 16), ("n_in_view", "<i4"), ("n_matches", "<i4"), ("n_edges", "<i4"),
+                            ("pnp_inliers", "<i4"), ("n_map_inliers", "<i4"), ("pad", "<i4", 3)])  # odo_local_map_result
 
 # Every symbol include/odo.h declares, with its ctypes signature.
 SIGNATURES = {
@@ -183,6 +191,9 @@ SIGNATURES = {
     "odo_chain_poses": (C.c_int, [P, C.c_int, P, P]),
     "odo_write_tum_trajectory": (C.c_int, [C.c_char_p, P, P, C.c_int, C.c_int]),
     "odo_projection_match": (C.c_int, [P, P, P, C.c_int, P, P, P, C.c_int, P, C.c_float, C.c_float, P, P, P]),
+    "odo_track_local_map": (C.c_int, [P, P, C.c_int, P, P, C.c_int, C.c_float, C.c_float, P]),
+    "odo_get_local_map": (C.c_int, [P, C.c_int, P, P, P, C.c_int]),
+    "odo_kp_capacity": (C.c_int, [P]),
     "odo_ransac_hyps": (C.c_int, [P, P, C.c_int, P, C.c_int, P, C.c_int, P, P, P, C.c_int, C.c_int, P, P]),
     "odo_ransac_fold": (C.c_int, [P, C.c_int, C.c_int, P, P]),
     "odo_ransac_hyps_finish": (C.c_int, [P, P, P, P, P, P, P, P, P]),

@@ -280,6 +280,27 @@ struct odo_ctx {
     } rb[2];
     bool ricp_alloc = false;
     int view_rb = 0;
+    // Batched TrackLocalMap scratch (odo_track_local_map), allocated by its
+    // first call: the per-frame arrays for max_batch frames, the per-landmark
+    // ones for lm_cap landmarks (regrown when a call brings more). lm_n: the
+    // landmarks of the last call while its batch is still the one in view
+    // (-1: odo_get_local_map has nothing to read)
+    struct LmBufs {
+        uint8_t* up = nullptr;  // the packed upload: poses, priors, landmarks
+        uint32_t* seen = nullptr;
+        int32_t *prior_eff = nullptr, *choice = nullptr, *over = nullptr, *slot = nullptr, *f2_src = nullptr;
+        uint8_t *taken0 = nullptr, *mask = nullptr, *outl = nullptr;
+        float2* bxy = nullptr;
+        uint32_t *bjo = nullptr, *cand = nullptr;
+        int *cstart = nullptr, *ccount = nullptr, *ints = nullptr;
+        float *proj = nullptr, *Xg = nullptr;
+        void* edges = nullptr;
+        odo_pair_result* pres = nullptr;
+        odo_local_map_result* res = nullptr;
+    } lm;
+    bool lm_alloc = false;
+    int lm_cap = 0, lm_n = -1;
+    LmGrid lm_grid{};
     // sequence state: the last tracked batch sits in frame set seq_set (its
     // last frame at slot seq_n); getters read view_set / view_n
     bool has_prev = false;
@@ -462,8 +483,51 @@ static int alloc_ricp(odo_ctx* c) {
     return ODO_OK;
 }
 
+// Batched TrackLocalMap scratch: max_batch frames, lm_cap landmarks
+static void free_local_map(odo_ctx* c) {
+    auto& L = c->lm;
+    void* pp[] = {L.up, L.seen, L.prior_eff, L.choice, L.over, L.slot, L.f2_src, L.taken0, L.mask, L.outl, L.bxy,
+                  L.bjo, L.cand, L.cstart, L.ccount, L.ints, L.proj, L.Xg, L.edges, L.pres, L.res};
+    for (void* q : pp)
+        if (q) (void)hipFree(q);
+    L = odo_ctx::LmBufs{};
+    c->lm_alloc = false;
+    c->lm_cap = 0;
+    c->lm_n = -1;
+}
+static int alloc_local_map(odo_ctx* c, int lm_cap) {
+    const size_t B = (size_t)c->maxb, KC = (size_t)c->kp_cap, LC = (size_t)lm_cap;
+    float bounds[4];
+    odo_image_bounds(c, bounds);
+    c->lm_grid = local_map_grid(bounds);
+    const size_t ncells = (size_t)c->lm_grid.gx * c->lm_grid.gy;
+    Pack pk;  // the largest upload: every section at its capacity
+    pk.add(B * 64);
+    pk.add(LC * sizeof(odo_landmark));
+    pk.add(B * KC * 4);
+    auto& L = c->lm;
+    int e;
+    if ((e = dalloc(&L.up, pk.off)) || (e = dalloc(&L.seen, B * ((LC + 31) / 32)))) return e;
+    if ((e = dalloc(&L.prior_eff, B * KC)) || (e = dalloc(&L.taken0, B * KC)) || (e = dalloc(&L.bxy, B * KC))) return e;
+    if ((e = dalloc(&L.bjo, B * KC)) || (e = dalloc(&L.cstart, B * (ncells + 1)))) return e;
+    if ((e = dalloc(&L.proj, B * LC * 3)) || (e = dalloc(&L.ccount, B * LC))) return e;
+    if ((e = dalloc(&L.cand, B * LC * local_map_cand_cap())) || (e = dalloc(&L.choice, B * LC))) return e;
+    if ((e = dalloc(&L.over, B * LC)) || (e = dalloc(&L.slot, B * KC)) || (e = dalloc(&L.f2_src, B * KC))) return e;
+    if ((e = dalloc(&L.Xg, B * KC * 3)) || (e = dalloc((uint8_t**)&L.edges, B * KC * pnp_edge_bytes()))) return e;
+    if ((e = dalloc(&L.pres, B)) || (e = dalloc(&L.mask, B * KC)) || (e = dalloc(&L.outl, B * KC))) return e;
+    if ((e = dalloc(&L.res, B)) || (e = dalloc(&L.ints, 2 * B))) return e;
+    // pair_valid = 1 and n_matches = 2^30 for every frame (launch_pnp's gates)
+    std::vector<int> ints(2 * B, 1);
+    std::fill(ints.begin() + B, ints.end(), 1 << 30);
+    HIPCHK(hipMemcpy(L.ints, ints.data(), ints.size() * sizeof(int), hipMemcpyHostToDevice));
+    c->lm_cap = lm_cap;
+    c->lm_alloc = true;
+    return ODO_OK;
+}
+
 static void free_ctx(odo_ctx* c) {
     if (!c) return;
+    free_local_map(c);
     free_hyp_session(c->hs);
     void* ptrs[] = {c->lv, c->cells, c->fsegs, c->rx, c->ry, c->pyr, c->blur, c->cand, c->cand_cnt, c->keys, c->knode,
                     c->okp, c->ocnt, c->kps, c->desc, c->kun, c->xyz, c->ur, c->nkp, c->bgr_in[0], c->depth_in[0],
@@ -1471,6 +1535,7 @@ int odo_extract_batch(odo_ctx* c, const uint8_t* d_bgr, const uint16_t* d_depth,
     if ((e = run_extract(c, set, d_bgr, d_depth, n, 1))) return e;
     c->view_set = set;
     c->last_n = n;
+    c->lm_n = -1;
     c->view_mode = -1;  // no pairs in view
     return ODO_OK;
 }
@@ -1712,6 +1777,7 @@ static int track_batch(odo_ctx* c, const uint8_t* d_bgr, const uint16_t* d_depth
     c->seq_n = n;
     c->view_set = s;
     c->last_n = n;
+    c->lm_n = -1;
     c->view_mode = (c->skip & 5) ? -1 : c->odo_mode;
     c->view_rb = (int)(c->batch_counter & 1);
     c->has_prev = true;
@@ -2297,6 +2363,7 @@ int odo_extract(odo_ctx* c, const uint8_t* img, int channels, const uint16_t* de
     }
     c->view_set = set;
     c->last_n = 1;
+    c->lm_n = -1;
     return odo_get_frame(c, 0, kps, desc, kps_un, xyz, u_right, cap, n);
 }
 
@@ -3012,6 +3079,119 @@ int odo_projection_match(odo_ctx* c, const float Tcw[16], const odo_landmark* lm
     HIPCHK(hipMemcpyAsync(n_matches, dnm.p, 4, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     return ODO_OK;
+}
+
+int odo_kp_capacity(odo_ctx* c) {
+    if (!c) return fail(ODO_ERR_ARG, "null ctx");
+    return c->kp_cap;
+}
+
+// Tracking::TrackLocalMap for the frames of the last batch, where they sit
+// (k_localmap.hip, then the batch's k_pnp over the gathered edges).
+constexpr int LM_MAX_LANDMARKS = 65536;
+int odo_track_local_map(odo_ctx* c, const odo_landmark* lms, int nL, const float* Tcw, const int32_t* prior, int kp_cap,
+                        float th, float nn_ratio, odo_local_map_result* results) {
+    if (!c || !Tcw || !results || nL < 0 || (nL && !lms)) return fail(ODO_ERR_ARG, "bad track_local_map args");
+    if (kp_cap != c->kp_cap) return fail(ODO_ERR_ARG, "track_local_map: kp_cap is not odo_kp_capacity()");
+    if (!(th >= 0.0f) || !std::isfinite(th)) return fail(ODO_ERR_ARG, "track_local_map: th must be finite and >= 0");
+    if (c->last_n <= 0) return fail(ODO_ERR_STATE, "track_local_map: no batch yet");
+    if (nL > LM_MAX_LANDMARKS) return fail(ODO_ERR_CAPACITY, "track_local_map: more than 65536 landmarks");
+    if (c->kp_cap > 8191) return fail(ODO_ERR_CAPACITY, "track_local_map: more than 8191 keypoints");
+    int e;
+    if ((e = sync_all(c))) return e;
+    c->lm_n = -1;
+    if (!c->lm_alloc || nL > c->lm_cap) {
+        free_local_map(c);
+        if ((e = alloc_local_map(c, std::max((nL + 1023) & ~1023, 4096)))) {  // all or nothing
+            free_local_map(c);
+            return e;
+        }
+    }
+    const int n = c->last_n;
+    const size_t KC = (size_t)c->kp_cap, fb = fbase(c, c->view_set);
+    auto& L = c->lm;
+    hipStream_t st = c->stream;
+    // poses, priors and landmarks packed into the pinned staging buffer, one upload
+    Pack pk;
+    const size_t o_T = pk.add((size_t)n * 64), o_lms = pk.add((size_t)nL * sizeof(odo_landmark)),
+                 o_prior = pk.add(prior ? (size_t)n * KC * 4 : 0);
+    const size_t up_bytes = pk.off;
+    if ((e = stage_reserve(c, std::max(up_bytes, (size_t)n * sizeof(odo_local_map_result))))) return e;
+    uint8_t* h = c->stage_h;
+    memcpy(h + o_T, Tcw, (size_t)n * 64);
+    if (nL) memcpy(h + o_lms, lms, (size_t)nL * sizeof(odo_landmark));
+    if (prior) memcpy(h + o_prior, prior, (size_t)n * KC * 4);
+    HIPCHK(hipMemcpyAsync(L.up, h, up_bytes, hipMemcpyHostToDevice, st));
+    const int seen_words = (c->lm_cap + 31) / 32;
+    HIPCHK(hipMemsetAsync(L.seen, 0, (size_t)n * seen_words * 4, st));
+    float b[4];
+    odo_image_bounds(c, b);
+    const odo_calib& k = c->cfg.calib;
+    LmSearch a{};
+    a.nframes = n;
+    a.nL = nL;
+    a.kp_cap = c->kp_cap;
+    a.seen_words = seen_words;
+    a.Tcw = reinterpret_cast<const float*>(L.up + o_T);
+    a.lms = reinterpret_cast<const odo_landmark*>(L.up + o_lms);
+    a.prior = prior ? reinterpret_cast<const int32_t*>(L.up + o_prior) : nullptr;
+    // slot 0 of the batch's frame set: frame i sits in slot i + 1
+    a.kun = c->kun + fb * KC * 2;
+    a.kps = c->kps + fb * KC;
+    a.desc = c->desc + fb * KC * 32;
+    a.nkp = c->nkp + fb;
+    a.G = c->lm_grid;
+    a.C = LmCalib{k.fx, k.fy, k.cx, k.cy, k.mbf, b[0], b[1], b[2], b[3]};
+    a.th = th;
+    a.nnratio = nn_ratio;
+    a.seen = L.seen;
+    a.prior_eff = L.prior_eff;
+    a.taken0 = L.taken0;
+    a.bxy = L.bxy;
+    a.bjo = L.bjo;
+    a.cstart = L.cstart;
+    a.proj = L.proj;
+    a.ccount = L.ccount;
+    a.cand = L.cand;
+    a.choice = L.choice;
+    a.over = L.over;
+    a.slot_lm = L.slot;
+    a.f2_src = L.f2_src;
+    a.Xg = L.Xg;
+    a.res = L.res;
+    if (launch_local_map_search(st, a) != 0) return fail(ODO_ERR_CAPACITY, "track_local_map capacity");
+    HIPCHK(hipGetLastError());
+    // the second PnPSolver::Compute: k_pnp with pair p = frame p, its "F1
+    // points" the gathered landmark positions (slot p of Xg), its F2 the
+    // frame's slot p + 1, from the pose passed in
+    launch_pnp(st, L.f2_src, L.Xg, a.kun, c->ur + fb * KC, a.nkp, c->kp_cap, 0, c->cal, a.Tcw, L.ints, L.ints + c->maxb,
+               0, L.edges, L.pres, L.mask, n);
+    HIPCHK(hipGetLastError());
+    launch_local_map_stats(st, a.lms, a.nkp, c->kp_cap, L.slot, L.mask, L.pres, L.outl, L.res, n);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(h, L.res, (size_t)n * sizeof(odo_local_map_result), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    memcpy(results, h, (size_t)n * sizeof(odo_local_map_result));
+    c->lm_n = nL;
+    return ODO_OK;
+}
+
+int odo_get_local_map(odo_ctx* c, int i, int32_t* slot_lm, float* proj, uint8_t* pnp_outlier, int cap) {
+    if (!c || !slot_lm || cap < 0) return fail(ODO_ERR_ARG, "bad get_local_map args");
+    if (c->lm_n < 0) return fail(ODO_ERR_STATE, "get_local_map: the last batch has no local-map results");
+    if (i < 0 || i >= c->last_n) return fail(ODO_ERR_ARG, "bad frame index");
+    int e;
+    if ((e = sync_all(c))) return e;
+    const size_t KC = (size_t)c->kp_cap, nL = (size_t)c->lm_n;
+    auto& L = c->lm;
+    int cnt = 0;
+    HIPCHK(hipMemcpy(&cnt, c->nkp + fbase(c, c->view_set) + i + 1, sizeof(int), hipMemcpyDeviceToHost));
+    cnt = std::min(cnt, c->kp_cap);
+    const size_t m = (size_t)std::max(0, std::min(cnt, cap));
+    if (m) HIPCHK(hipMemcpy(slot_lm, L.slot + (size_t)i * KC, m * 4, hipMemcpyDeviceToHost));
+    if (pnp_outlier && m) HIPCHK(hipMemcpy(pnp_outlier, L.outl + (size_t)i * KC, m, hipMemcpyDeviceToHost));
+    if (proj && nL) HIPCHK(hipMemcpy(proj, L.proj + (size_t)i * nL * 3, nL * 12, hipMemcpyDeviceToHost));
+    return cnt > cap ? fail(ODO_ERR_CAPACITY, "cap too small") : ODO_OK;
 }
 
 int odo_chain_poses(const odo_pair_result* res, int n, const float Tcw_prev[16], float* out) {

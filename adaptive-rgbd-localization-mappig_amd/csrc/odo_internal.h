@@ -351,6 +351,49 @@ int launch_projection_match(hipStream_t st, const float* Tcw, const odo_landmark
                             const float* calib5, const float* bounds, float th, float nnratio, float* proj,
                             uint8_t* inview, int* ccount, uint32_t* cand, int32_t* slot_lm, int* nmatches);
 size_t projection_cand_cap();
+// Batched TrackLocalMap (k_localmap.hip), nframes frames in batch slots 1 ..
+// nframes of the arrays kun / kps / desc / nkp point at (slot 0's base).
+struct LmGrid {
+    float x0, y0, inv;  // origin (minX, minY) and 1 / cell size of the keypoint grid
+    int gx, gy;
+};
+struct LmCalib {
+    float fx, fy, cx, cy, mbf;
+    float minX, maxX, minY, maxY;
+};
+struct LmSearch {
+    int nframes, nL, kp_cap, seen_words;
+    const float* Tcw;            // nframes x 16
+    const odo_landmark* lms;     // nL
+    const int32_t* prior;        // nframes x kp_cap or null
+    const float* kun;
+    const orb_kp* kps;
+    const uint8_t* desc;
+    const int* nkp;
+    LmGrid G;
+    LmCalib C;
+    float th, nnratio;
+    uint32_t* seen;              // nframes x seen_words, zeroed by the caller
+    int32_t* prior_eff;          // nframes x kp_cap
+    uint8_t* taken0;             // nframes x kp_cap
+    float2* bxy;                 // nframes x kp_cap
+    uint32_t* bjo;               // nframes x kp_cap
+    int* cstart;                 // nframes x (gx * gy + 1)
+    float* proj;                 // nframes x nL x 3
+    int* ccount;                 // nframes x nL
+    uint32_t* cand;              // nframes x local_map_cand_cap() x nL
+    int32_t *choice, *over;      // nframes x nL each
+    int32_t *slot_lm, *f2_src;   // nframes x kp_cap each
+    float* Xg;                   // nframes x kp_cap x 3
+    odo_local_map_result* res;   // nframes
+};
+int local_map_cand_cap();
+LmGrid local_map_grid(const float bounds[4]);
+// prior, bins, candidates, resolve, merge and edge gather; -1: kp_cap above 8191
+int launch_local_map_search(hipStream_t st, const LmSearch& a);
+void launch_local_map_stats(hipStream_t st, const odo_landmark* lms, const int* nkp, int kp_cap, const int32_t* slot_lm,
+                            const uint8_t* pnp_mask, const odo_pair_result* pres, uint8_t* outlier,
+                            odo_local_map_result* res, int nframes);
 void upload_adaptive_constants();
 void launch_adapt_smap(hipStream_t st, const uint8_t* pyr, size_t pyr_stride, int w, int h, int pitch, uint8_t* smap,
                        size_t smap_stride, int nframes);

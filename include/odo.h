@@ -389,6 +389,62 @@ int odo_projection_match(odo_ctx* ctx, const float Tcw[16], const odo_landmark* 
                          const uint8_t* slot_taken, float th, float nn_ratio, int32_t* slot_lm, float* proj,
                          int* n_matches);
 
+/* ---- Batched Tracking::TrackLocalMap (tracking.cpp:231-261, 368-405): the
+ * local-map search and the second PnPSolver::Compute for every frame of the
+ * LAST BATCH, the n frames odo_get_frame(ctx, i, ...) reads (after any
+ * odo_track_batch* or odo_extract_batch). The frames are read where they sit
+ * in HBM: keypoints, octaves, descriptors and right coordinates are not
+ * uploaded. One launch chain for all frames, on odo_stream().
+ *
+ * Frame i, pose Tcw[i] (world -> camera, 4x4 row-major; typically
+ * odo_chain_poses output), against the one shared landmark array lms:
+ *   prior   prior_slot_lm[i * kp_cap + j] = k >= 0: slot j already holds
+ *           lms[k] when TrackLocalMap starts (a map landmark KnnMatch carried
+ *           over); -1 (or an index outside [0, n_lms)): empty; NULL: every
+ *           slot empty. kp_cap must be odo_kp_capacity(ctx). A prior slot
+ *           whose landmark is ODO_LM_BAD is released first (UpdateLocalKFs,
+ *           tracking.cpp:270-276); every remaining prior landmark counts as
+ *           ODO_LM_SEEN for that frame only (tracking.cpp:371-382, 388); the
+ *           slot is taken iff its landmark has ODO_LM_HAS_OBS
+ *           (matcher.cpp:114-117). A landmark may appear in at most one prior
+ *           slot of a frame (not checked).
+ *   search  Frame::isInFrustum and Matcher(nn_ratio)::ProjectionMatch(th)
+ *           exactly as odo_projection_match defines them, landmarks in index
+ *           order (the reference passes 0.8f and 8.0f).
+ *   slots   slot j holds the landmark the search put there, else its
+ *           surviving prior, else -1.
+ *   PnP     PnPSolver::Compute (pnpsolver.cpp:17) over every slot holding a
+ *           landmark, in slot order, from Tcw[i]: Xw = the landmark's X, the
+ *           observation (kps_un[j], u_right[j]) (mono when u_right < 0),
+ *           information 1 / Xw.z^2 with the world z (pnpsolver.cpp:74,111).
+ *           Fewer than 3 edges: pnp_inliers = 0 and the pose as given.
+ * No carry between frames (the batched contract): frame i's
+ * refined pose does not feed frame i + 1 inside the call; every frame starts
+ * from the pose the caller passes.
+ *
+ * The call synchronises the context, uploads landmarks, poses and priors in
+ * one transfer, and returns with results[0 .. n) filled (one download); slots,
+ * projections and masks stay in HBM for odo_get_local_map. n_lms == 0 is valid
+ * (zeros and the input poses). Scratch is allocated by the first call (and
+ * grown when a later call brings more landmarks); a context that never calls
+ * this allocates and launches nothing for it.
+ * ODO_ERR_STATE: no batch yet. ODO_ERR_ARG: NULL ctx / Tcw / results (or lms
+ * with n_lms > 0), kp_cap != odo_kp_capacity(ctx), th negative or not finite,
+ * n_lms < 0. ODO_ERR_CAPACITY: more than 65536 landmarks, or a keypoint
+ * capacity above 8191 (13-bit keypoint index in a candidate). */
+int odo_track_local_map(odo_ctx* ctx, const odo_landmark* lms, int n_lms, const float* Tcw,
+                        const int32_t* prior_slot_lm, int kp_cap, float th, float nn_ratio,
+                        odo_local_map_result* results);
+/* Frame i of the last odo_track_local_map (ODO_ERR_STATE when the last batch
+ * has none): slot_lm[j] for the frame's keypoints (up to cap; more keypoints
+ * than cap: ODO_ERR_CAPACITY after copying cap), proj (optional): n_lms x 3
+ * (mTrackProjX, mTrackProjY, mTrackProjXR), NaN for landmarks not in view;
+ * pnp_outlier (optional, cap): 1 for a slot whose landmark the second PnP
+ * flagged as an outlier. Synchronises. */
+int odo_get_local_map(odo_ctx* ctx, int i, int32_t* slot_lm, float* proj, uint8_t* pnp_outlier, int cap);
+/* Keypoint slots per frame of the context: the row length of prior_slot_lm. */
+int odo_kp_capacity(odo_ctx* ctx);
+
 /* Kabsch::Compute (kabsch.cpp:14): one GPU workgroup (k_kabsch: centroids, A^T B
  * with a fixed-order block reduction, 3x3 Jacobi SVD). A,B: n x 3 host arrays.
  * R = W diag(1, 1, sgn(det V det W)) V^T is a rotation for every input (the

@@ -165,6 +165,19 @@ typedef struct odo_ricp_result {
     int32_t pad[3];
 } odo_ricp_result;
 
+/* Tracking::TrackLocalMap for one frame of the last batch (odo_track_local_map).
+ * 96 bytes. */
+typedef struct odo_local_map_result {
+    float   Tcw[16];        /* pose after the second PnPSolver::Compute (the input pose when it does not run) */
+    int32_t n_in_view;      /* landmarks isInFrustum accepted (nToMatch, tracking.cpp:394-397) */
+    int32_t n_matches;      /* ProjectionMatch's return (0 when n_in_view == 0: it is not called) */
+    int32_t n_edges;        /* slots holding a landmark when PnP starts */
+    int32_t pnp_inliers;    /* PnPSolver::Compute's return */
+    int32_t n_map_inliers;  /* inlier slots whose landmark has ODO_LM_HAS_OBS (TrackLocalMap's nInliers,
+                               tracking.cpp:247-255) */
+    int32_t pad[3];         /* pad[0]: diagnostic, the rounds the slot resolver ran for the frame; the rest 0 */
+} odo_local_map_result;
+
 #ifdef __cplusplus
 }
 #endif

@@ -522,6 +522,19 @@ class Odometry:
                                       max_corr_dist, ptr(T), ptr(conv), ptr(it), ptr(nc)))
         return [(T[p].reshape(4, 4), int(conv[p]), int(it[p]), int(nc[p])) for p in range(P)]
 
+    def gicp_covariances(self, clouds):
+        """GICP's computeCovariances (k_gicp_cov alone) for a list of n x 3 clouds
+        in one launch. Returns a list of n x 3 x 3 float64 arrays (zeros for a
+        cloud under 20 points). Raises if the kernel's source and target sets
+        differ (odo_gicp_covariances)."""
+        offs = np.zeros(len(clouds) + 1, np.int32)
+        offs[1:] = np.cumsum([len(c) for c in clouds])
+        P = np.ascontiguousarray(np.concatenate([np.asarray(c, np.float32).reshape(-1, 3) for c in clouds])
+                                 if clouds else np.zeros((0, 3), np.float32))
+        Cv = np.full((max(int(offs[-1]), 1), 9), np.nan)
+        check(self.lib.odo_gicp_covariances(self.h, ptr(P), ptr(offs), len(clouds), ptr(Cv)))
+        return [Cv[offs[p]:offs[p + 1]].reshape(-1, 3, 3) for p in range(len(clouds))]
+
     def timings(self):
         ms = np.zeros(16, np.float32)
         names = (C.c_char_p * 16)()

@@ -772,11 +772,15 @@ __global__ __launch_bounds__(GI_THREADS) void k_gicp(const float* __restrict__ s
 
 }  // namespace
 
+void launch_gicp_cov(hipStream_t st, const float* src, const int* soffs, double* Cs, const float* tgt,
+                     const int* toffs, double* Ct, int nprob, int max_n) {
+    const int nbx = (max_n + 63) / 64;
+    hipLaunchKernelGGL(k_gicp_cov, dim3(nbx, nprob, 2), dim3(64), 0, st, src, soffs, Cs, tgt, toffs, Ct, 1e-3);
+}
+
 void launch_gicp(hipStream_t st, const float* src, const float* tgt, int nprob, int max_ns, int max_nt, double* Cs,
                  double* Ct, float* outp, double* Mah, int* is, int* it, GicpArgs args, float* T12, int* outi) {
-    const int nbx = (std::max(max_ns, max_nt) + 63) / 64;
-    hipLaunchKernelGGL(k_gicp_cov, dim3(nbx, nprob, 2), dim3(64), 0, st, src, args.soffs, Cs, tgt, args.toffs, Ct,
-                       1e-3);
+    launch_gicp_cov(st, src, args.soffs, Cs, tgt, args.toffs, Ct, nprob, std::max(max_ns, max_nt));
     hipLaunchKernelGGL(k_gicp, dim3(nprob), dim3(GI_THREADS), 0, st, src, tgt, Cs, Ct, outp, Mah, is, it, args, T12,
                        outi);
 }

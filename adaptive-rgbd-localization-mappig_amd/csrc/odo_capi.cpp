@@ -2997,6 +2997,45 @@ int odo_gicp_batch(odo_ctx* c, const float* src, const int32_t* soffs, const flo
                     iterations, n_corr);
 }
 
+int odo_gicp_covariances(odo_ctx* c, const float* P, const int32_t* offs, int nprob, double* C) {
+    if (!c || nprob < 0 || !offs) return fail(ODO_ERR_ARG, "bad gicp_covariances args");
+    if (nprob == 0) return ODO_OK;
+    if (offs[0] != 0) return fail(ODO_ERR_ARG, "gicp_covariances: offsets must start at 0");
+    if (nprob > 65535) return fail(ODO_ERR_CAPACITY, "gicp_covariances: more than 65535 clouds per call");
+    int max_n = 0;
+    for (int p = 0; p < nprob; p++) {
+        const int n = offs[p + 1] - offs[p];
+        if (n < 0) return fail(ODO_ERR_ARG, "gicp_covariances: offsets must not decrease");
+        if (n > 16384) return fail(ODO_ERR_CAPACITY, "gicp_covariances: more than 16384 points in a cloud");
+        max_n = std::max(max_n, n);
+    }
+    const size_t N = (size_t)offs[nprob], np = (size_t)nprob;
+    if (N == 0) return ODO_OK;
+    if (!P || !C) return fail(ODO_ERR_ARG, "bad gicp_covariances args");
+    memset(C, 0, N * 72);  // k_gicp_cov skips clouds under 20 points
+    if (max_n < 20) return ODO_OK;
+    hipStream_t st = c->stream;
+    DevArena& A = c->arena;
+    A.begin();
+    DevBuf dp(A, N * 12), dCs(A, N * 72), dCt(A, N * 72), doff(A, (np + 1) * 4);
+    ARENA_CHECK(A);
+    HIPCHK(hipMemcpyAsync(dp.p, P, N * 12, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(doff.p, offs, (np + 1) * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(dCs.p, 0, N * 72, st));
+    HIPCHK(hipMemsetAsync(dCt.p, 0, N * 72, st));
+    // the batch in both roles: the source set is returned, the target set must repeat it
+    launch_gicp_cov(st, dp.as<float>(), doff.as<int>(), dCs.as<double>(), dp.as<float>(), doff.as<int>(),
+                    dCt.as<double>(), nprob, max_n);
+    HIPCHK(hipGetLastError());
+    std::vector<double> Ct(N * 9);
+    HIPCHK(hipMemcpyAsync(C, dCs.p, N * 72, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(Ct.data(), dCt.p, N * 72, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (memcmp(C, Ct.data(), N * 72) != 0)
+        return fail(ODO_ERR_DEVICE, "gicp_covariances: the source and the target set differ");
+    return ODO_OK;
+}
+
 // Frame::ComputeImageBounds: cv::undistortPoints of the four corners (5
 // iterations in double, App. A.10)
 static void undistort_host(float u, float v, const odo_calib& c, float* uo, float* vo) {

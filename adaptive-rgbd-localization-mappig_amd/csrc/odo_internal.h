@@ -318,6 +318,11 @@ struct GicpArgs {
 };
 void launch_gicp(hipStream_t st, const float* src, const float* tgt, int nprob, int max_ns, int max_nt, double* Cs,
                  double* Ct, float* outp, double* Mah, int* is, int* it, GicpArgs args, float* T12, int* outi);
+// launch_gicp's first launch by itself: k_gicp_cov on the source and target
+// clouds of nprob problems (a problem with a cloud under 20 points is skipped,
+// its rows of Cs / Ct are not written); max_n = the longest cloud of either side
+void launch_gicp_cov(hipStream_t st, const float* src, const int* soffs, double* Cs, const float* tgt,
+                     const int* toffs, double* Ct, int nprob, int max_n);
 // Batched ADAPTIVE_RICP / RANSAC back-ends (k_ricp.hip), on the pair stream
 // after launch_ransac. The branch rule's constants (odometry.cpp:52-53):
 struct RicpCfg {

@@ -354,6 +354,18 @@ int odo_gicp_batch(odo_ctx* ctx, const float* src, const int32_t* soffs, const f
                    const float* guesses, int nprob, int max_iterations, double max_corr_dist, float* T12,
                    int32_t* converged, int32_t* iterations, int32_t* n_corr);
 
+/* GICP's computeCovariances by itself (the first launch of odo_gicp /
+ * odo_gicp_batch, k_gicp_cov), for tests and diagnosis: cloud p = points
+ * [offs[p], offs[p+1]) of P (n x 3; offsets start at 0, nprob + 1 entries); C
+ * receives 9 doubles per point, the row-major 3 x 3 covariance of the point's 20
+ * nearest neighbours in its own cloud with the eigenvalues replaced by
+ * (1, 1, 1e-3). A cloud under 20 points gets zeros (GICP does not run on it).
+ * The kernel works on a source and a target set per call: the batch is given
+ * to it in both roles, C is the source set, and ODO_ERR_DEVICE is returned if
+ * the target set differs from it in any bit. At most 16384 points per cloud
+ * (ODO_ERR_CAPACITY). */
+int odo_gicp_covariances(odo_ctx* ctx, const float* P, const int32_t* offs, int nprob, double* C);
+
 /* ---- Trajectory (host only) ----
  * Relative-pose chain of the batched contract: results[i].Tcw is frame i's
  * pose in frame i-1's camera coordinates, so Tcw(i) = Tcw_rel(i) * Tcw(i-1)

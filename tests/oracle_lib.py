@@ -387,3 +387,11 @@ def gicp(src, tgt, guess=None, max_iterations=10, max_corr_dist=0.07):
     ok = lib().oracle_gicp(ptr(src), len(src), ptr(tgt), len(tgt), ptr(g), max_iterations, max_corr_dist, ptr(T),
                            C.byref(conv), C.byref(it), C.byref(nc))
     return dict(ok=ok, T=T.reshape(4, 4), converged=conv.value, iterations=it.value, n_corr=nc.value)
+
+
+def gicp_covariances(P):
+    """computeCovariances on the oracle: n x 3 x 3 float64 (n >= 20)."""
+    P = np.ascontiguousarray(P, np.float32)
+    Cv = np.zeros((len(P), 9))
+    lib().oracle_gicp_covariances(ptr(P), len(P), ptr(Cv))
+    return Cv.reshape(-1, 3, 3)

@@ -17,7 +17,8 @@ from ._abi import (DETECTOR_ADAPTIVE_FAST, DETECTOR_ADAPTIVE_ORB, DETECTOR_ORB_S
                    AdaptiveParams, Calib, Config, DMatch, PnPRansacResult,
                    DMATCH_DTYPE, KP_DTYPE, LANDMARK_DTYPE, LOCAL_MAP_DTYPE, LM_BAD, LM_HAS_OBS, LM_SEEN, LocalMapResult,
                    OrbParams, PAIR_DTYPE, PairResult, RansacParams, Rng, check, load, ptr,
-                   ODOMETRY_ADAPTIVE_RBA, ODOMETRY_ADAPTIVE_RICP, ODOMETRY_RANSAC, RicpParams, RicpResult)
+                   ODOMETRY_ADAPTIVE_RBA, ODOMETRY_ADAPTIVE_RICP, ODOMETRY_RANSAC, RicpParams, RicpResult,
+                   BA_EDGE_DTYPE, BA_NOTHING, BA_RAN, BaParams, BaResult)
 
 __all__ = ["Odometry", "HostFrames", "PinnedResults", "default_config", "load", "KP_DTYPE", "DMATCH_DTYPE", "PAIR_DTYPE", "rng_stream",
            "kabsch", "Calib", "OrbParams", "RansacParams", "Config", "AdaptiveParams", "DETECTOR_ORB_SLAM2",
@@ -25,7 +26,8 @@ __all__ = ["Odometry", "HostFrames", "PinnedResults", "default_config", "load", 
            "PYRAMID_FORM_AUTO", "PYRAMID_FORM_FUSED", "PYRAMID_FORM_CHAIN",
            "PYRAMID_FORM_FUSED_NOBLUR", "ODOMETRY_ADAPTIVE_RBA", "ODOMETRY_RANSAC", "ODOMETRY_ADAPTIVE_RICP",
            "RicpParams", "RicpResult", "default_ricp_params", "LANDMARK_DTYPE", "LOCAL_MAP_DTYPE", "LocalMapResult",
-           "LM_BAD", "LM_SEEN", "LM_HAS_OBS"]
+           "LM_BAD", "LM_SEEN", "LM_HAS_OBS", "BA_EDGE_DTYPE", "BaParams", "BaResult", "BA_RAN", "BA_NOTHING",
+           "default_ba_params"]
 
 
 def default_config(width=640, height=480, max_batch=1, nfeatures=1000, iterations=200, seed=0x5EED0000,
@@ -50,6 +52,14 @@ def default_config(width=640, height=480, max_batch=1, nfeatures=1000, iteration
     for k, v in (forms or {}).items():  # odo_kernel_forms: bit-identical kernel alternatives
         setattr(cfg.forms, k, v)
     return cfg
+
+
+def default_ba_params() -> BaParams:
+    """odo_default_ba_params: the constants of localbundleadjustment.cpp (5 robust
+    iterations, 10 final ones, Huber sqrt(5.991) / sqrt(7.815), chi2 5.991 / 7.815)."""
+    p = BaParams()
+    load().odo_default_ba_params(ptr(p))
+    return p
 
 
 def default_ricp_params() -> RicpParams:
@@ -383,6 +393,26 @@ class Odometry:
         check(self.lib.odo_track_local_map(self.h, ptr(lms), len(lms), ptr(T), ptr(pr), kc, th, nn_ratio, ptr(out)))
         self._lm_n = len(lms)
         return out
+
+    def local_ba(self, Tcw, kf_fixed, Xw, edges, calib: Calib = None, params: BaParams = None):
+        """odo_local_ba: LocalBundleAdjustment::Compute (localbundleadjustment.cpp:65-315)
+        on the device. Tcw: n_kf x 4 x 4 poses (world -> camera); kf_fixed: n_kf
+        (non-zero: the keyframe is fixed); Xw: n_lm x 3; edges: BA_EDGE_DTYPE
+        array (ur < 0: monocular). With params.iters_final = 0 it is
+        GlobalBundleAdjustment. The inputs are not modified. Returns
+        (Tcw n_kf x 4 x 4, Xw n_lm x 3, erase uint8 per edge, BaResult)."""
+        T = np.array(Tcw, np.float32, order="C").reshape(-1, 16)
+        X = np.array(Xw, np.float32, order="C").reshape(-1, 3)
+        fx = np.ascontiguousarray(np.asarray(kf_fixed) != 0, np.uint8).reshape(-1)
+        if len(fx) != len(T):
+            raise ValueError(f"kf_fixed has {len(fx)} entries for {len(T)} poses")
+        E = np.ascontiguousarray(edges, BA_EDGE_DTYPE).reshape(-1)
+        erase = np.zeros(len(E), np.uint8)
+        res = BaResult()
+        check(self.lib.odo_local_ba(self.h, ptr(T), ptr(fx), len(T), ptr(X), len(X), ptr(E), len(E),
+                                    ptr(calib) if calib is not None else None,
+                                    ptr(params) if params is not None else None, ptr(erase), ptr(res)))
+        return T.reshape(-1, 4, 4), X, erase, res
 
     def local_map(self, i: int):
         """odo_get_local_map: frame i of the last track_local_map. Returns

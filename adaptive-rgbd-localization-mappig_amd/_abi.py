@@ -85,6 +85,21 @@ class LocalMapResult(C.Structure):
                 ("pnp_inliers", C.c_int32), ("n_map_inliers", C.c_int32), ("pad", C.c_int32 * 3)]
 
 
+class BaParams(C.Structure):
+    """odo_ba_params (include/odo_types.h): the constants of localbundleadjustment.cpp."""
+    _fields_ = [("iters_robust", C.c_int32), ("iters_final", C.c_int32), ("robust", C.c_int32),
+                ("huber_mono", C.c_float), ("huber_stereo", C.c_float), ("chi2_mono", C.c_float),
+                ("chi2_stereo", C.c_float)]
+
+
+class BaResult(C.Structure):
+    """odo_ba_result (include/odo_types.h)."""
+    _fields_ = [("chi2_initial", C.c_double), ("chi2_stage1", C.c_double), ("chi2_final", C.c_double),
+                ("iters1", C.c_int32), ("iters2", C.c_int32), ("trials1", C.c_int32), ("trials2", C.c_int32),
+                ("n_erase", C.c_int32), ("n_level1", C.c_int32), ("status", C.c_int32), ("pad", C.c_int32)]
+
+
+BA_RAN, BA_NOTHING = 0, 1  # include/odo_types.h ODO_BA_*
 ODOMETRY_ADAPTIVE_RBA = 0   # include/odo.h ODO_ODOMETRY_ADAPTIVE_RBA
 ODOMETRY_RANSAC = 1         # include/odo.h ODO_ODOMETRY_RANSAC
 ODOMETRY_ADAPTIVE_RICP = 2  # include/odo.h ODO_ODOMETRY_ADAPTIVE_RICP
@@ -125,6 +140,7 @@ class FoldResult(C.Structure):
 HYP_DTYPE = np.dtype([("err", "<f8"), ("cnt", "<i4"), ("pad", "<i4"), ("T", "<f4", 12)])  # odo_hyp_summary
 LANDMARK_DTYPE = np.dtype([("X", "<f4", 3), ("flags", "<i4"), ("desc", "u1", 32)])  # odo_landmark
 LM_BAD, LM_SEEN, LM_HAS_OBS = 1, 2, 4
+BA_EDGE_DTYPE = np.dtype([("kf", "<i4"), ("lm", "<i4"), ("u", "<f4"), ("v", "<f4"), ("ur", "<f4")])  # odo_ba_edge
 KP_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4"),
                      ("response", "<f4"), ("octave", "<i4"), ("class_id", "<i4")])
 DMATCH_DTYPE = np.dtype([("queryIdx", "<i4"), ("trainIdx", "<i4"), ("imgIdx", "<i4"), ("distance", "<f4")])
@@ -195,6 +211,8 @@ SIGNATURES = {
     "odo_track_local_map": (C.c_int, [P, P, C.c_int, P, P, C.c_int, C.c_float, C.c_float, P]),
     "odo_get_local_map": (C.c_int, [P, C.c_int, P, P, P, C.c_int]),
     "odo_kp_capacity": (C.c_int, [P]),
+    "odo_default_ba_params": (None, [P]),
+    "odo_local_ba": (C.c_int, [P, P, P, C.c_int, P, C.c_int, P, C.c_int, P, P, P, P]),
     "odo_ransac_hyps": (C.c_int, [P, P, C.c_int, P, C.c_int, P, C.c_int, P, P, P, C.c_int, C.c_int, P, P]),
     "odo_ransac_fold": (C.c_int, [P, C.c_int, C.c_int, P, P]),
     "odo_ransac_hyps_finish": (C.c_int, [P, P, P, P, P, P, P, P, P]),

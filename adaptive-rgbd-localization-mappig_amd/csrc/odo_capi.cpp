@@ -301,6 +301,10 @@ struct odo_ctx {
     bool lm_alloc = false;
     int lm_cap = 0, lm_n = -1;
     LmGrid lm_grid{};
+    // odo_local_ba's device block (upload, download and kernel scratch),
+    // allocated by its first call and regrown when a call needs more
+    uint8_t* ba_dev = nullptr;
+    size_t ba_cap = 0;
     // sequence state: the last tracked batch sits in frame set seq_set (its
     // last frame at slot seq_n); getters read view_set / view_n
     bool has_prev = false;
@@ -528,6 +532,7 @@ static int alloc_local_map(odo_ctx* c, int lm_cap) {
 static void free_ctx(odo_ctx* c) {
     if (!c) return;
     free_local_map(c);
+    if (c->ba_dev) (void)hipFree(c->ba_dev);
     free_hyp_session(c->hs);
     void* ptrs[] = {c->lv, c->cells, c->fsegs, c->rx, c->ry, c->pyr, c->blur, c->cand, c->cand_cnt, c->keys, c->knode,
                     c->okp, c->ocnt, c->kps, c->desc, c->kun, c->xyz, c->ur, c->nkp, c->bgr_in[0], c->depth_in[0],
@@ -3212,6 +3217,174 @@ int odo_track_local_map(odo_ctx* c, const odo_landmark* lms, int nL, const float
     HIPCHK(hipStreamSynchronize(st));
     memcpy(results, h, (size_t)n * sizeof(odo_local_map_result));
     c->lm_n = nL;
+    return ODO_OK;
+}
+
+// LocalBundleAdjustment::Compute (k_ba.hip): validation, the two CSRs, one
+// upload, the Levenberg loop (ba_run), one download.
+void odo_default_ba_params(odo_ba_params* p) {
+    if (!p) return;
+    p->iters_robust = 5;
+    p->iters_final = 10;
+    p->robust = 1;
+    p->huber_mono = sqrtf(5.991f);
+    p->huber_stereo = sqrtf(7.815f);
+    p->chi2_mono = 5.991f;
+    p->chi2_stereo = 7.815f;
+}
+
+constexpr int BA_MAX_FREE = 64, BA_MAX_KF = 256, BA_MAX_LM = 65536, BA_MAX_EDGES = 1 << 20;
+int odo_local_ba(odo_ctx* c, float* Tcw, const uint8_t* kf_fixed, int n_kf, float* Xw, int n_lm, const odo_ba_edge* edges,
+                 int n_edges, const odo_calib* calib, const odo_ba_params* params, uint8_t* edge_erase,
+                 odo_ba_result* result) {
+    if (!c || !result || n_kf < 0 || n_lm < 0 || n_edges < 0 || (n_kf && (!Tcw || !kf_fixed)) || (n_lm && !Xw) ||
+        (n_edges && (!edges || !edge_erase)))
+        return fail(ODO_ERR_ARG, "bad local_ba args");
+    odo_ba_params P;
+    if (params) P = *params;
+    else odo_default_ba_params(&P);
+    if (P.iters_robust < 1 || P.iters_final < 0 || !(P.huber_mono > 0.f) || !(P.huber_stereo > 0.f) ||
+        !std::isfinite(P.huber_mono) || !std::isfinite(P.huber_stereo) || !(P.chi2_mono > 0.f) || !(P.chi2_stereo > 0.f))
+        return fail(ODO_ERR_ARG, "local_ba: bad params (iters_robust >= 1, iters_final >= 0, positive thresholds)");
+    if (n_kf > BA_MAX_KF) return fail(ODO_ERR_CAPACITY, "local_ba: more than 256 keyframes");
+    if (n_lm > BA_MAX_LM) return fail(ODO_ERR_CAPACITY, "local_ba: more than 65536 landmarks");
+    if (n_edges > BA_MAX_EDGES) return fail(ODO_ERR_CAPACITY, "local_ba: more than 2^20 edges");
+    std::vector<int32_t> pidx((size_t)std::max(n_kf, 1), -1);
+    int nf = 0;
+    for (int k = 0; k < n_kf; k++)
+        if (!kf_fixed[k]) pidx[k] = nf++;
+    if (nf > BA_MAX_FREE) return fail(ODO_ERR_CAPACITY, "local_ba: more than 64 free keyframes");
+    for (size_t i = 0; i < (size_t)n_kf * 16; i++)
+        if (!std::isfinite(Tcw[i])) return fail(ODO_ERR_ARG, "local_ba: non-finite pose");
+    for (size_t i = 0; i < (size_t)n_lm * 3; i++)
+        if (!std::isfinite(Xw[i])) return fail(ODO_ERR_ARG, "local_ba: non-finite landmark");
+    for (int l = 0; l < n_lm; l++) {
+        const float z = Xw[3 * (size_t)l + 2];
+        if (!std::isfinite(1.0f / (z * z)))  // z == 0, or so small that z * z underflows
+            return fail(ODO_ERR_ARG, "local_ba: a landmark with infinite information (z * z == 0 in float)");
+    }
+    // the CSRs by landmark and by keyframe, both in edge order (counting sorts)
+    std::vector<int32_t> lstart((size_t)n_lm + 1, 0), kstart((size_t)n_kf + 1, 0), lorder((size_t)std::max(n_edges, 1)),
+        korder((size_t)std::max(n_edges, 1));
+    for (int e = 0; e < n_edges; e++) {
+        const odo_ba_edge& E = edges[e];
+        if (E.kf < 0 || E.kf >= n_kf || E.lm < 0 || E.lm >= n_lm) return fail(ODO_ERR_ARG, "local_ba: edge index out of range");
+        if (!std::isfinite(E.u) || !std::isfinite(E.v) || !std::isfinite(E.ur))
+            return fail(ODO_ERR_ARG, "local_ba: non-finite observation");
+        lstart[(size_t)E.lm + 1]++;
+        kstart[(size_t)E.kf + 1]++;
+    }
+    for (int l = 0; l < n_lm; l++) lstart[(size_t)l + 1] += lstart[l];
+    for (int k = 0; k < n_kf; k++) kstart[(size_t)k + 1] += kstart[k];
+    {
+        std::vector<int32_t> lpos(lstart.begin(), lstart.end() - 1), kpos(kstart.begin(), kstart.end() - 1);
+        for (int e = 0; e < n_edges; e++) {
+            lorder[lpos[edges[e].lm]++] = e;
+            korder[kpos[edges[e].kf]++] = e;
+        }
+        // at most one edge per (keyframe, landmark): the Schur kernel's items rely on it
+        std::vector<int32_t> stamp((size_t)std::max(n_kf, 1), -1);
+        for (int l = 0; l < n_lm; l++)
+            for (int q = lstart[l]; q < lstart[(size_t)l + 1]; q++) {
+                const int k = edges[lorder[q]].kf;
+                if (stamp[k] == l) return fail(ODO_ERR_ARG, "local_ba: a (keyframe, landmark) pair appears in two edges");
+                stamp[k] = l;
+            }
+    }
+    memset(result, 0, sizeof(*result));
+    if (n_edges == 0) {  // nothing to optimise: no vertex has an edge
+        result->status = ODO_BA_NOTHING;
+        return ODO_OK;
+    }
+    int e0;
+    if ((e0 = sync_all(c))) return e0;
+    hipStream_t st = c->stream;
+    const size_t NK = (size_t)n_kf, NL = (size_t)n_lm, NE = (size_t)n_edges;
+    Pack pk;
+    const size_t o_T = pk.add(NK * 64), o_X = pk.add(NL * 12), o_pidx = pk.add(NK * 4), o_insys = pk.add(NK),
+                 o_ekf = pk.add(NE * 4), o_elm = pk.add(NE * 4), o_obs = pk.add(NE * 12), o_ls = pk.add((NL + 1) * 4),
+                 o_lo = pk.add(NE * 4), o_ks = pk.add((NK + 1) * 4), o_ko = pk.add(NE * 4);
+    const size_t up_bytes = pk.off;
+    const size_t o_oT = pk.add(NK * 64), o_oX = pk.add(NL * 12), o_er = pk.add(NE), o_cnt = pk.add(16);
+    const size_t io_bytes = pk.off, o_scal = pk.add(64);
+    const size_t need = io_bytes + ba_scratch_bytes(n_kf, n_lm, n_edges, nf);
+    if ((e0 = stage_reserve(c, pk.off))) return e0;
+    if (need > c->ba_cap) {
+        if (c->ba_dev) (void)hipFree(c->ba_dev);
+        c->ba_dev = nullptr;
+        c->ba_cap = 0;
+        const size_t cap = std::max(need, (size_t)1 << 20);
+        if (hipMalloc((void**)&c->ba_dev, cap) != hipSuccess) return fail(ODO_ERR_DEVICE, "local_ba: hipMalloc failed");
+        c->ba_cap = cap;
+    }
+    uint8_t* h = c->stage_h;
+    memcpy(h + o_T, Tcw, NK * 64);
+    memcpy(h + o_X, Xw, NL * 12);
+    memcpy(h + o_pidx, pidx.data(), NK * 4);
+    for (int k = 0; k < n_kf; k++) h[o_insys + k] = (pidx[k] >= 0 && kstart[(size_t)k + 1] > kstart[k]) ? 1 : 0;
+    {
+        int32_t* ekf = reinterpret_cast<int32_t*>(h + o_ekf);
+        int32_t* elm = reinterpret_cast<int32_t*>(h + o_elm);
+        float* ob = reinterpret_cast<float*>(h + o_obs);
+        for (int e = 0; e < n_edges; e++) {
+            ekf[e] = edges[e].kf;
+            elm[e] = edges[e].lm;
+            ob[3 * (size_t)e] = edges[e].u;
+            ob[3 * (size_t)e + 1] = edges[e].v;
+            ob[3 * (size_t)e + 2] = edges[e].ur;
+        }
+    }
+    memcpy(h + o_ls, lstart.data(), (NL + 1) * 4);
+    memcpy(h + o_lo, lorder.data(), NE * 4);
+    memcpy(h + o_ks, kstart.data(), (NK + 1) * 4);
+    memcpy(h + o_ko, korder.data(), NE * 4);
+    uint8_t* d = c->ba_dev;
+    HIPCHK(hipMemcpyAsync(d, h, up_bytes, hipMemcpyHostToDevice, st));
+    const odo_calib& k = calib ? *calib : c->cfg.calib;
+    BaArgs a{};
+    a.nk = n_kf;
+    a.nl = n_lm;
+    a.ne = n_edges;
+    a.nf = nf;
+    a.Tcw = reinterpret_cast<const float*>(d + o_T);
+    a.Xw = reinterpret_cast<const float*>(d + o_X);
+    a.eobs = reinterpret_cast<const float*>(d + o_obs);
+    a.ekf = reinterpret_cast<const int32_t*>(d + o_ekf);
+    a.elm = reinterpret_cast<const int32_t*>(d + o_elm);
+    a.lstart = reinterpret_cast<const int32_t*>(d + o_ls);
+    a.lorder = reinterpret_cast<const int32_t*>(d + o_lo);
+    a.kstart = reinterpret_cast<const int32_t*>(d + o_ks);
+    a.korder = reinterpret_cast<const int32_t*>(d + o_ko);
+    a.pidx = reinterpret_cast<const int32_t*>(d + o_pidx);
+    a.insys = d + o_insys;
+    a.oT = reinterpret_cast<float*>(d + o_oT);
+    a.oX = reinterpret_cast<float*>(d + o_oX);
+    a.erase = d + o_er;
+    a.counts = reinterpret_cast<int32_t*>(d + o_cnt);
+    a.scratch = d + io_bytes;
+    a.h_scal = reinterpret_cast<double*>(h + o_scal);
+    a.fx = (double)k.fx;
+    a.fy = (double)k.fy;
+    a.cx = (double)k.cx;
+    a.cy = (double)k.cy;
+    a.bf = (double)k.mbf;
+    odo_ba_result r{};
+    const hipError_t he = ba_run(st, a, P, &r);
+    if (he != hipSuccess) {
+        (void)hipStreamSynchronize(st);
+        return fail(ODO_ERR_DEVICE, std::string("local_ba: ") + hipGetErrorString(he));
+    }
+    HIPCHK(hipMemcpyAsync(h + o_oT, d + o_oT, io_bytes - o_oT, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    int32_t cnt[4];
+    memcpy(cnt, h + o_cnt, sizeof(cnt));
+    r.n_level1 = cnt[0];
+    r.n_erase = cnt[1];
+    r.status = ODO_BA_RAN;
+    memcpy(Tcw, h + o_oT, NK * 64);
+    memcpy(Xw, h + o_oX, NL * 12);
+    memcpy(edge_erase, h + o_er, NE);
+    *result = r;
     return ODO_OK;
 }
 

@@ -305,6 +305,26 @@ void launch_pnp(hipStream_t st, const int32_t* f2_src, const float* xyz, const f
                 const int* n_matches, int min_matches, void* edges, odo_pair_result* res, uint8_t* inlier_mask,
                 int npairs, const int* sel = nullptr, int sel_val = 0);
 void launch_kabsch(hipStream_t st, const float* A, const float* B, int n, float* T);
+// Local bundle adjustment (k_ba.hip). Device pointers unless noted: the
+// uploaded problem (edges, their CSRs by landmark and by keyframe in edge
+// order, pidx[k] = index of keyframe k among the free ones or -1, insys[k] =
+// free and observed), the download block (oT nk x 16, oX nl x 3, erase ne,
+// counts: level-1 marks, erase marks) and ba_scratch_bytes() of scratch.
+// h_scal: 8 doubles of pinned host memory for the per-trial scalars.
+struct BaArgs {
+    int nk, nl, ne, nf;
+    const float *Tcw, *Xw, *eobs;
+    const int32_t *ekf, *elm, *lstart, *lorder, *kstart, *korder, *pidx;
+    const uint8_t* insys;
+    float *oT, *oX;
+    uint8_t* erase;
+    int32_t* counts;
+    void* scratch;
+    double* h_scal;
+    double fx, fy, cx, cy, bf;
+};
+size_t ba_scratch_bytes(int nk, int nl, int ne, int nf);
+hipError_t ba_run(hipStream_t st, const BaArgs& a, const odo_ba_params& p, odo_ba_result* res);
 // GICP (k_gicp.hip), nprob problems: source p = points [soffs[p], soffs[p+1]) of
 // src, target p = [toffs[p], toffs[p+1]) of tgt. Cs sum(ns)*9, Ct sum(nt)*9,
 // outp sum(ns)*3, Mah sum(ns)*9, is / it sum(ns); T12 16 and outi 4 per problem.

@@ -457,6 +457,69 @@ int odo_get_local_map(odo_ctx* ctx, int i, int32_t* slot_lm, float* proj, uint8_
 /* Keypoint slots per frame of the context: the row length of prior_slot_lm. */
 int odo_kp_capacity(odo_ctx* ctx);
 
+/* ---- LocalBundleAdjustment::Compute (localbundleadjustment.cpp:65-315) on
+ * the device: g2o OptimizationAlgorithmLevenberg over SE3Expmap pose vertices
+ * and marginalised XYZ point vertices, BlockSolver_6_3 + LinearSolverEigen,
+ * optimize(iters_robust) with the Huber kernel, the chi2 / depth
+ * classification (:223-254), optimize(iters_final) on the level-0 edges
+ * without it, and the erase list (:261-285). The caller does the graph walk
+ * of :21-63 (map bookkeeping) and passes flat arrays:
+ *   Tcw      n_kf x 16, world -> camera, row-major, in / out (:85, :302-307)
+ *   kf_fixed n_kf: 1 = the vertex is fixed (lFixedCameras and keyframe id 0, :87, :99)
+ *   Xw       n_lm x 3 world positions, in / out (:133, :310-315)
+ *   edges    n_edges observations (kf, lm, u, v, ur), ur < 0 monocular; a
+ *            landmark holds at most one edge per keyframe (GetObservations
+ *            is a map keyed by keyframe, :139)
+ *   edge_erase[e] = 1: the reference would EraseLandmark / EraseObservation
+ *            this pair (:290-297)
+ * Semantics (DESIGN.md §2 lists the pinned choices):
+ *   vertices  poses are SE3Quat from the float matrix (Converter::toSE3Quat),
+ *            points double from float; update T <- exp(dx) T, X <- X + dl
+ *   edges    error = obs - project(T X), third row u - bf / z for stereo; the
+ *            pose Jacobian of odo_pnp_motion_ba, the point Jacobian
+ *            -(d proj / d Xc) R; information 1.0f / (z * z) in float from the
+ *            landmark's INITIAL world z (:158, :185), the same for all its
+ *            edges, never updated
+ *   optimize lambda0 = 1e-5 max |diag H| over all active pose and point blocks
+ *            at the start of each optimize(); lambda on every diagonal; scale
+ *            = sum x (lambda x + b) + 1e-3; a trial is rejected when rho <= 0,
+ *            its chi2 is not finite or the solve failed; at most 10 trials;
+ *            stop when the trials reach 10 or rho == 0
+ *   solve    Hll^-1 per 3 x 3 block, S = Hpp - sum W Hll^-1 W^T, LDL^T without
+ *            pivoting failing iff a pivot is exactly zero (the step of a
+ *            failed solve is zero), points by back-substitution
+ *   flags    after stage 1 an edge with chi2 > chi2_mono / chi2_stereo or
+ *            (T X).z <= 0 goes to level 1; the chi2 is the one g2o has stored,
+ *            of the LAST TRIAL EVALUATED (also a rejected one); the depth
+ *            test uses the current estimates; a level-1 edge keeps its chi2.
+ *            A landmark or free pose without a level-0 edge leaves the system
+ *            and keeps its estimate. edge_erase: the same test after stage 2.
+ *   outputs  cast to float; a fixed keyframe, a free keyframe without an edge
+ *            and a landmark without an edge come back bit for bit
+ * GlobalBundleAdjustment (globalbundleadjustment.cpp:151-152) is the same call
+ * with iters_final = 0, iters_robust = nIterations and its Huber deltas
+ * sqrt(5.99) / sqrt(7.815) in the params.
+ * Not supported: the abort flag (pbStopFlag, :76, :208-219).
+ * Deviations: a non-finite pose, point or observation, a landmark whose
+ * 1.0f / (z * z) is infinite (z == 0, or z * z underflows in float; infinite
+ * information in the reference), an edge index out of range or a
+ * repeated (kf, lm) pair give ODO_ERR_ARG without a launch, the caller's
+ * arrays untouched. n_edges == 0 (or no free keyframe and no landmark with an
+ * edge) is valid: status = ODO_BA_NOTHING, inputs unchanged, nothing launched.
+ * ODO_ERR_CAPACITY: more than 64 free keyframes, 256 keyframes, 65536
+ * landmarks or 2^20 edges. One upload and one download; between them only
+ * three scalars per Levenberg trial reach the host. Scratch is allocated by
+ * the first call and grown by later ones; a context that never calls this
+ * allocates and launches nothing for it. Bit-identical run to run. The call
+ * synchronises the context first (like odo_track_local_map) and returns with
+ * the outputs written; the last batch's results stay readable.
+ * ODO_ERR_ARG also for iters_robust < 1, iters_final < 0 or a threshold <= 0.
+ * calib NULL: the context's; params NULL: odo_default_ba_params. */
+void odo_default_ba_params(odo_ba_params* p);
+int odo_local_ba(odo_ctx* ctx, float* Tcw, const uint8_t* kf_fixed, int n_kf, float* Xw, int n_lm,
+                 const odo_ba_edge* edges, int n_edges, const odo_calib* calib, const odo_ba_params* params,
+                 uint8_t* edge_erase, odo_ba_result* result);
+
 /* Kabsch::Compute (kabsch.cpp:14): one GPU workgroup (k_kabsch: centroids, A^T B
  * with a fixed-order block reduction, 3x3 Jacobi SVD). A,B: n x 3 host arrays.
  * R = W diag(1, 1, sgn(det V det W)) V^T is a rotation for every input (the

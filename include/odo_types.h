@@ -178,6 +178,39 @@ typedef struct odo_local_map_result {
     int32_t pad[3];         /* pad[0]: diagnostic, the rounds the slot resolver ran for the frame; the rest 0 */
 } odo_local_map_result;
 
+/* One reprojection edge of odo_local_ba: keyframe kf observes landmark lm at
+ * the undistorted keypoint (u, v) with right coordinate ur; ur < 0: a
+ * monocular observation (localbundleadjustment.cpp:149). 20 bytes. */
+typedef struct odo_ba_edge {
+    int32_t kf, lm;
+    float   u, v, ur;
+} odo_ba_edge;
+
+/* The constants of LocalBundleAdjustment::Compute made explicit
+ * (odo_default_ba_params: localbundleadjustment.cpp:126-127, 213, 230, 244, 254). */
+typedef struct odo_ba_params {
+    int32_t iters_robust;   /* 5   first optimize(), Huber on                                        */
+    int32_t iters_final;    /* 10  second optimize() on level-0 edges, Huber off; 0 = skip stage 2  */
+    int32_t robust;         /* 1   Huber in stage 1                                                  */
+    float   huber_mono, huber_stereo;   /* sqrtf(5.991), sqrtf(7.815) as floats                      */
+    float   chi2_mono, chi2_stereo;     /* 5.991, 7.815                                              */
+} odo_ba_params;
+
+/* What odo_local_ba did. 64 bytes. */
+#define ODO_BA_RAN 0       /* the optimiser ran */
+#define ODO_BA_NOTHING 1   /* nothing to optimise: the inputs came back, nothing was launched */
+typedef struct odo_ba_result {
+    double  chi2_initial;   /* robust chi2 before the first iteration                  */
+    double  chi2_stage1;    /* after the first optimize()                              */
+    double  chi2_final;     /* after the second (= chi2_stage1 when it did not run)    */
+    int32_t iters1, iters2;     /* iterations each optimize() ran                      */
+    int32_t trials1, trials2;   /* Levenberg trials (linear solves) of each            */
+    int32_t n_erase;        /* edges flagged in edge_erase                             */
+    int32_t n_level1;       /* edges set aside after stage 1                           */
+    int32_t status;         /* ODO_BA_*                                                */
+    int32_t pad;
+} odo_ba_result;
+
 #ifdef __cplusplus
 }
 #endif

@@ -44,7 +44,7 @@ namespace odo {
 // size (host). Source and destination levels alternate between two LDS
 // buffers; every level is also written to the frame's cell-pyramid buffer
 // (pitched rows, zero padding). Resize tables are made in LDS with the
-// generic-path rules of App. A.2 (the host rules of odo_capi.cpp
+// generic-path rules of App. A.2 (the host rules of odo_geometry.cpp
 // build_geometry).
 // LDS = false (cells too large for the two LDS level buffers, e.g. 1280x960
 // frames): every level reads its source level back from the cell-pyramid

@@ -1,6 +1,6 @@
 // ORB-SLAM2 extraction kernels for gfx950 (Features/orbextractor.cpp,
 // Core/frame.cpp). One launch processes a batch of frames; all per-level
-// geometry lives in device tables built once per image size (odo_capi.cpp).
+// geometry lives in device tables built once per image size (odo_geometry.cpp).
 //
 //   k_gray        cvtColor(BGR2GRAY)                 frame.cpp:23
 //   k_resize      ComputePyramid (INTER_LINEAR 8U)    orbextractor.cpp:833-857

@@ -1,5 +1,5 @@
 // Internal (non-ABI) structures shared by the HIP kernels and the host
-// orchestration in odo_capi.cpp.
+// orchestration (odo_*.cpp, whose own shared header is odo_ctx.h).
 #pragma once
 
 #include <hip/hip_runtime.h>

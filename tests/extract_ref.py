@@ -621,7 +621,7 @@ def scaled_keypoints(level, x, y, scale):
 
 
 def segments(cells, wcell, seg_cells=8, row_bytes=272):
-    """k_fast_seg's segments of one level, restating odo_capi.cpp:727-732: each
+    """k_fast_seg's segments of one level, restating odo_geometry.cpp build_geometry: each
     cell row's ncj cells in nseg = ceil(ncj / kmax) even runs, kmax = min(8,
     (272 - 15 - 6) / wCell), run sg = cells [ncj sg / nseg, ncj (sg + 1) / nseg)
     of the row. Returns a list of index arrays into `cells`."""

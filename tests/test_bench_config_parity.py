@@ -260,7 +260,7 @@ def test_bench_configuration_latched():
     """Two batches, a host sync, then six more without one: from the third
     batch on the DepthCovariance latch is known to be set (k_latch's host flag
     after its event completed) and the batches leave the latch kernel and its
-    ordering packets out (odo_capi.cpp run_pairs). Every pair of the last
+    ordering packets out (odo_batch.cpp run_pairs). Every pair of the last
     batch bit-exact, the latch included."""
     name = "cfg2_latched"
     c = dict(CONFIGS["cfg2_bench"], batches=8, sync_after=1)

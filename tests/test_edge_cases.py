@@ -137,3 +137,60 @@ def test_gpu_far_scenes_vo_landmark_sort_path(scale):
         assert np.array_equal(res[p]["T12"], np.array(r.T12, np.float32)), f"pair {p}: T12"
         assert np.abs(res[p]["Tcw"] - np.array(r.Tcw, np.float32)).max() < 1e-4, f"pair {p}: Tcw"
     odo.close()
+
+
+def _drive_every_lazy_block(pkg, bgr, dep, ba):
+    """One context through everything it allocates on demand, then close()."""
+    cfg = pkg.default_config(160, 120, 2, nfeatures=300, iterations=64)
+    cfg.orb.nlevels = 4  # the 120-row image keeps 40 rows down to level 3
+    odo = pkg.Odometry(cfg)
+    odo.track_batch_host(bgr, dep)
+    odo.set_odometry(pkg.ODOMETRY_ADAPTIVE_RICP)  # the GICP scratch of both pair streams
+    odo.track_batch_host(bgr, dep)
+    rs = np.random.default_rng(5)
+    for n_lms in (8, 5000):  # the first call allocates for 4096 landmarks, the second regrows
+        lms = np.zeros(n_lms, pkg.LANDMARK_DTYPE)
+        lms["X"] = rs.uniform([-1, -1, 1], [1, 1, 4], (n_lms, 3))
+        lms["desc"] = rs.integers(0, 256, (n_lms, 32))
+        odo.track_local_map(lms, np.tile(np.eye(4, dtype=np.float32), (2, 1, 1)))
+    cal = pkg.Calib()
+    cal.fx, cal.fy, cal.cx, cal.cy, cal.mbf = ba.Cam.fx, ba.Cam.fy, ba.Cam.cx, ba.Cam.cy, ba.Cam.bf
+    c = ba.ba_case(ba.CASES[0])
+    _, _, _, r = odo.local_ba(c["Tcw"], c["fixed"], c["Xw"], c["edges"], cal)
+    assert r.status == pkg.BA_RAN
+    # one hypotheses-mode session: 40 matches of a cloud with itself
+    x = np.ascontiguousarray(rs.uniform([-1, -1, 1], [1, 1, 4], (40, 3)), np.float32)
+    m = np.zeros(40, pkg.DMATCH_DTYPE)
+    m["queryIdx"] = m["trainIdx"] = np.arange(40)
+    m["distance"] = rs.permutation(40)
+    lib, rng = pkg.load(), pkg.Rng()
+    lib.odo_rng_seed(pkg.ptr(rng), 1)
+    lat, ng = O.C.c_double(float("nan")), O.C.c_int(0)
+    hyps = np.zeros(64, pkg._abi.HYP_DTYPE)
+    pkg.check(lib.odo_ransac_hyps(odo.h, pkg.ptr(m), 40, pkg.ptr(x), 40, pkg.ptr(x), 40,
+                                  pkg.ptr(pkg.RansacParams(64, 20, 3.0, 4, 1)), pkg.ptr(rng), O.C.byref(lat), 0, 64,
+                                  pkg.ptr(hyps), O.C.byref(ng)))
+    assert ng.value == 40
+    odo.close()
+
+
+@pytest.mark.gpu
+def test_gpu_context_lifetime_returns_all_device_memory():
+    """create -> every lazily allocated block once -> close, three times, with
+    a context of each ADAPTIVE detector created and closed in between: the
+    device's free memory after the third close is not below the reading after
+    the first (which absorbs the runtime's own one-time allocations). Exact:
+    no tolerance."""
+    import torch
+    import ba_ref64 as ba
+    pkg = load_pkg()
+    bgr, dep, _ = sequence(2, w=160, h=120, seed=0x5EED000D)
+    bgr, dep = np.ascontiguousarray(bgr), np.ascontiguousarray(dep)
+    free = []
+    for _ in range(3):
+        _drive_every_lazy_block(pkg, bgr, dep, ba)
+        for det in (pkg.DETECTOR_ADAPTIVE_FAST, pkg.DETECTOR_ADAPTIVE_ORB):
+            pkg.Odometry(pkg.default_config(640, 480, 1, detector=det)).close()
+        torch.cuda.synchronize()
+        free.append(torch.cuda.mem_get_info()[0])
+    assert free[2] >= free[0], f"device memory lost over two create/close cycles: {free[0] - free[2]} bytes ({free})"

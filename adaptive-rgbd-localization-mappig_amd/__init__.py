@@ -18,7 +18,8 @@ from ._abi import (DETECTOR_ADAPTIVE_FAST, DETECTOR_ADAPTIVE_ORB, DETECTOR_ORB_S
                    DMATCH_DTYPE, KP_DTYPE, LANDMARK_DTYPE, LOCAL_MAP_DTYPE, LM_BAD, LM_HAS_OBS, LM_SEEN, LocalMapResult,
                    OrbParams, PAIR_DTYPE, PairResult, RansacParams, Rng, check, load, ptr,
                    ODOMETRY_ADAPTIVE_RBA, ODOMETRY_ADAPTIVE_RICP, ODOMETRY_RANSAC, RicpParams, RicpResult,
-                   BA_EDGE_DTYPE, BA_NOTHING, BA_RAN, BaParams, BaResult)
+                   BA_EDGE_DTYPE, BA_NOTHING, BA_RAN, BaParams, BaResult,
+                   FUSE_BAD, FUSE_BEHIND, FUSE_CAND_DTYPE, FUSE_CANDS, FUSE_KF_DTYPE, FUSE_NULL, FUSE_OUTSIDE)
 
 __all__ = ["Odometry", "HostFrames", "PinnedResults", "default_config", "load", "KP_DTYPE", "DMATCH_DTYPE", "PAIR_DTYPE", "rng_stream",
            "kabsch", "Calib", "OrbParams", "RansacParams", "Config", "AdaptiveParams", "DETECTOR_ORB_SLAM2",
@@ -27,7 +28,8 @@ __all__ = ["Odometry", "HostFrames", "PinnedResults", "default_config", "load", 
            "PYRAMID_FORM_FUSED_NOBLUR", "ODOMETRY_ADAPTIVE_RBA", "ODOMETRY_RANSAC", "ODOMETRY_ADAPTIVE_RICP",
            "RicpParams", "RicpResult", "default_ricp_params", "LANDMARK_DTYPE", "LOCAL_MAP_DTYPE", "LocalMapResult",
            "LM_BAD", "LM_SEEN", "LM_HAS_OBS", "BA_EDGE_DTYPE", "BaParams", "BaResult", "BA_RAN", "BA_NOTHING",
-           "default_ba_params"]
+           "default_ba_params", "fuse_best", "FUSE_KF_DTYPE", "FUSE_CAND_DTYPE", "FUSE_CANDS", "FUSE_NULL", "FUSE_BAD",
+           "FUSE_BEHIND", "FUSE_OUTSIDE"]
 
 
 def default_config(width=640, height=480, max_batch=1, nfeatures=1000, iterations=200, seed=0x5EED0000,
@@ -414,6 +416,37 @@ class Odometry:
                                     ptr(params) if params is not None else None, ptr(erase), ptr(res)))
         return T.reshape(-1, 4, 4), X, erase, res
 
+    def fuse_search(self, kfs, lms, lm_index, th: float = 4.0):
+        """odo_fuse_search: the search of Matcher::Fuse (matcher.cpp:212-291) for
+        every Fuse call of LocalMapping::FuseLandmarks in one device call. kfs:
+        one (Tcw 4 x 4, kps_un n x 2, u_right n, desc n x 32, (lm_begin, lm_end))
+        per call, its list the entries [lm_begin, lm_end) of lm_index (indices
+        into lms; < 0 or >= len(lms): a null pointer); lms: LANDMARK_DTYPE array.
+        Returns a FUSE_CAND_DTYPE array, one record per (call, list entry) in
+        call order then list order; candidate indices are the keyframe's own."""
+        lms = np.ascontiguousarray(lms, LANDMARK_DTYPE).reshape(-1)
+        idx = np.ascontiguousarray(lm_index, np.int32).reshape(-1)
+        K = np.zeros(len(kfs), FUSE_KF_DTYPE)
+        kun, ur, desc, row = [], [], [], 0
+        for k, (T, p, r, d, (lo, hi)) in enumerate(kfs):
+            p = np.asarray(p, np.float32).reshape(-1, 2)
+            r = np.asarray(r, np.float32).reshape(-1)
+            d = np.asarray(d, np.uint8).reshape(-1, 32)
+            if not len(p) == len(r) == len(d):
+                raise ValueError(f"keyframe {k}: {len(p)} keypoints, {len(r)} right coordinates, {len(d)} descriptors")
+            K[k] = (np.asarray(T, np.float32).reshape(16), row, row + len(p), lo, hi)
+            row += len(p)
+            kun.append(p)
+            ur.append(r)
+            desc.append(d)
+        kun = np.ascontiguousarray(np.concatenate(kun)) if kun else np.zeros((0, 2), np.float32)
+        ur = np.ascontiguousarray(np.concatenate(ur)) if ur else np.zeros(0, np.float32)
+        desc = np.ascontiguousarray(np.concatenate(desc)) if desc else np.zeros((0, 32), np.uint8)
+        out = np.zeros(int(np.maximum(K["lm_end"] - K["lm_begin"], 0).sum()), FUSE_CAND_DTYPE)
+        check(self.lib.odo_fuse_search(self.h, ptr(K), len(K), ptr(kun), ptr(ur), ptr(desc), row, ptr(lms), len(lms),
+                                       ptr(idx), len(idx), th, ptr(out)))
+        return out
+
     def local_map(self, i: int):
         """odo_get_local_map: frame i of the last track_local_map. Returns
         dict(slot_lm nkp, proj n_lms x 3 (NaN: not in view), pnp_outlier nkp)."""
@@ -578,6 +611,23 @@ def rng_stream(seed: int, n: int) -> np.ndarray:
     L = load()
     L.odo_rng_seed(ptr(r), seed)
     return np.array([L.odo_rng_next(ptr(r)) for _ in range(n)], np.int32)
+
+
+def fuse_best(rec, kps_un, u_right, desc, new_desc, th: float = 4.0):
+    """odo_fuse_best (host only): Fuse's (bestIdx, bestDist) of one fuse_search
+    record under another descriptor. kps_un / u_right / desc: the record's
+    keyframe; over rec["cand"] when n_cand <= 8, else the keyframe is scanned
+    again with the window and the gate from the record's projection. Returns
+    (-1, INT32_MAX) when nothing is gated."""
+    r = np.ascontiguousarray(rec, FUSE_CAND_DTYPE).reshape(-1)[:1]
+    p = np.ascontiguousarray(kps_un, np.float32).reshape(-1, 2)
+    u = np.ascontiguousarray(u_right, np.float32).reshape(-1)
+    d = np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
+    nd = np.ascontiguousarray(new_desc, np.uint8).reshape(32)
+    bi, bd = C.c_int32(0), C.c_int32(0)
+    check(load().odo_fuse_best(ptr(r), ptr(p), ptr(u), ptr(d), len(p), th, ptr(nd), C.cast(C.byref(bi), C.c_void_p),
+                               C.cast(C.byref(bd), C.c_void_p)))
+    return bi.value, bd.value
 
 
 def pair_seed(base: int, pair: int) -> int:

@@ -149,6 +149,12 @@ PAIR_DTYPE = np.dtype([("T12", "<f4", 16), ("Tcw", "<f4", 16), ("rmse", "<f4"), 
                        ("visited", "<i4"), ("n_queries", "<i4"), ("n_sweeps", "<i4"), ("n_fit_points", "<i4")])
 LOCAL_MAP_DTYPE = np.dtype([("Tcw", "<f4", 16), ("n_in_view", "<i4"), ("n_matches", "<i4"), ("n_edges", "<i4"),
                             ("pnp_inliers", "<i4"), ("n_map_inliers", "<i4"), ("pad", "<i4", 3)])  # odo_local_map_result
+FUSE_KF_DTYPE = np.dtype([("Tcw", "<f4", 16), ("kp_begin", "<i4"), ("kp_end", "<i4"), ("lm_begin", "<i4"),
+                          ("lm_end", "<i4")])  # odo_fuse_kf
+FUSE_CANDS = 8  # include/odo_types.h ODO_FUSE_CANDS
+FUSE_CAND_DTYPE = np.dtype([("u", "<f4"), ("v", "<f4"), ("ur", "<f4"), ("n_cand", "<i4"), ("best_idx", "<i4"),
+                            ("best_dist", "<i4"), ("cand", "<u2", FUSE_CANDS)])  # odo_fuse_cand
+FUSE_NULL, FUSE_BAD, FUSE_BEHIND, FUSE_OUTSIDE = -1, -2, -3, -4  # include/odo_types.h ODO_FUSE_*
 
 # Every symbol include/odo.h declares, with its ctypes signature.
 SIGNATURES = {
@@ -211,6 +217,8 @@ SIGNATURES = {
     "odo_track_local_map": (C.c_int, [P, P, C.c_int, P, P, C.c_int, C.c_float, C.c_float, P]),
     "odo_get_local_map": (C.c_int, [P, C.c_int, P, P, P, C.c_int]),
     "odo_kp_capacity": (C.c_int, [P]),
+    "odo_fuse_search": (C.c_int, [P, P, C.c_int, P, P, P, C.c_int, P, C.c_int, P, C.c_int, C.c_float, P]),
+    "odo_fuse_best": (C.c_int, [P, P, P, P, C.c_int, C.c_float, P, P, P]),
     "odo_default_ba_params": (None, [P]),
     "odo_local_ba": (C.c_int, [P, P, P, C.c_int, P, C.c_int, P, C.c_int, P, P, P, P]),
     "odo_ransac_hyps": (C.c_int, [P, P, C.c_int, P, C.c_int, P, C.c_int, P, P, P, C.c_int, C.c_int, P, P]),

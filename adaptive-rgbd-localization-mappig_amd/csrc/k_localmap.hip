@@ -41,6 +41,7 @@
 //   k_lm_stats    after k_pnp: n_map_inliers, the outlier flags, the record
 #include "odo_device.h"
 #include "odo_internal.h"
+#include "odo_kpgrid.h"
 
 namespace odo {
 
@@ -49,13 +50,6 @@ namespace odo {
 #define LMK_OBS (1 << 30)  // in a candidate count: the landmark has observations
 #define LMK_NT 1024  // k_lm_resolve threads
 #define LMK_NW (LMK_NT / 64)
-
-ODO_INLINE int lmk_hamming(const uint32_t* a, const uint8_t* b8) {
-    const uint4* b = reinterpret_cast<const uint4*>(b8);
-    const uint4 x = b[0], y = b[1];
-    return __popc(a[0] ^ x.x) + __popc(a[1] ^ x.y) + __popc(a[2] ^ x.z) + __popc(a[3] ^ x.w) + __popc(a[4] ^ y.x) +
-           __popc(a[5] ^ y.y) + __popc(a[6] ^ y.z) + __popc(a[7] ^ y.w);
-}
 
 // key order = (distance, keypoint index): keypoint 13 bits, octave 5, distance 9
 ODO_INLINE uint32_t lmk_key(int j, int oct, int d) {
@@ -73,25 +67,6 @@ ODO_INLINE int lmk_decide(uint32_t k1, uint32_t k2, float nnratio) {
     if (!(best1 <= 100.0)) return -1;
     if (k2 != LMK_NONE && (k1 & 31) == (k2 & 31) && best1 > (double)nnratio * (double)(k2 >> 18)) return -1;
     return (int)((k1 >> 5) & 0x1fff);
-}
-
-// cell of coordinate t (relative to the grid origin), clamped: monotone in t,
-// so a point inside [lo, hi] lies in a cell of [cell(lo), cell(hi)]
-ODO_INLINE int lmk_cell(float t, float inv, int g) {
-    return (int)fminf(fmaxf(floorf(t * inv), 0.0f), (float)(g - 1));
-}
-// the cells a +-th window around (u, v) can touch; one pixel of margin covers
-// the rounding of u +- th against the window test's own fabsf(x - u) < th
-struct LmkRange {
-    int cx0, cx1, cy0, cy1;
-};
-ODO_INLINE LmkRange lmk_range(float u, float v, float th, const LmGrid& G) {
-    LmkRange r;
-    r.cx0 = lmk_cell((u - th - 1.0f) - G.x0, G.inv, G.gx);
-    r.cx1 = lmk_cell((u + th + 1.0f) - G.x0, G.inv, G.gx);
-    r.cy0 = lmk_cell((v - th - 1.0f) - G.y0, G.inv, G.gy);
-    r.cy1 = lmk_cell((v + th + 1.0f) - G.y0, G.inv, G.gy);
-    return r;
 }
 
 __global__ void __launch_bounds__(256) k_lm_prior(const int32_t* __restrict__ prior, const odo_landmark* __restrict__ lms,

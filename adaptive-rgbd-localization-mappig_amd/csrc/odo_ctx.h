@@ -298,6 +298,10 @@ struct odo_ctx {
     // allocated by its first call and regrown when a call needs more
     uint8_t* ba_dev = nullptr;
     size_t ba_cap = 0;
+    // odo_fuse_search's device block (upload, records, sorted points and cell
+    // starts), allocated by its first call and regrown when a call needs more
+    uint8_t* fuse_dev = nullptr;
+    size_t fuse_cap = 0;
     // sequence state: the last tracked batch sits in frame set seq_set (its
     // last frame at slot seq_n); getters read view_set / view_n
     bool has_prev = false;

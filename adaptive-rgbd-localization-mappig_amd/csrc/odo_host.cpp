@@ -1,8 +1,53 @@
 // The parts of the C-ABI that need no device: the glibc rand() restatement,
-// the hypotheses fold, pose chaining and the TUM trajectory writer.
+// the hypotheses fold, pose chaining, the TUM trajectory writer and the
+// re-scoring of a Fuse record.
 #include "odo_ctx.h"
 
+static_assert(sizeof(odo_fuse_kf) == 80 && sizeof(odo_fuse_cand) == 40, "odo_fuse_* layout");
+
 extern "C" {
+
+// matcher.cpp:256-291 over the record's gated keypoints (k_fuse_search's
+// window and gate, the same float operations in the same order)
+int odo_fuse_best(const odo_fuse_cand* rec, const float* kun, const float* ur, const uint8_t* desc, int n, float th,
+                  const uint8_t new_desc[32], int32_t* best_idx, int32_t* best_dist) {
+    if (!rec || !new_desc || !best_idx || !best_dist || n < 0 || (n && (!kun || !ur || !desc)))
+        return fail(ODO_ERR_ARG, "bad fuse_best args");
+    if (!(th >= 0.0f) || !std::isfinite(th)) return fail(ODO_ERR_ARG, "fuse_best: th must be finite and >= 0");
+    int bi = -1, bd = INT32_MAX;
+    auto visit = [&](int j) {
+        int d = 0;
+        for (int k = 0; k < 32; k++) d += __builtin_popcount((unsigned)(new_desc[k] ^ desc[32 * (size_t)j + k]));
+        if (d < bd) {
+            bd = d;
+            bi = j;
+        }
+    };
+    if (rec->n_cand > ODO_FUSE_CANDS) {
+        const float u = rec->u, v = rec->v, r = rec->ur;
+        for (int j = 0; j < n; j++) {
+            const float dx = kun[2 * j] - u, dy = kun[2 * j + 1] - v;
+            if (!(fabsf(dx) < th && fabsf(dy) < th)) continue;
+            const float ex = u - kun[2 * j], ey = v - kun[2 * j + 1];
+            float e2 = ex * ex + ey * ey, lim = 5.99f;
+            if (ur[j] >= 0.0f) {
+                const float er = r - ur[j];
+                e2 = e2 + er * er;
+                lim = 7.8f;
+            }
+            if (e2 > lim) continue;
+            visit(j);
+        }
+    } else {
+        for (int k = 0; k < rec->n_cand; k++) {
+            if (rec->cand[k] >= n) return fail(ODO_ERR_ARG, "fuse_best: a candidate outside the keyframe");
+            visit(rec->cand[k]);
+        }
+    }
+    *best_idx = bi;
+    *best_dist = bd;
+    return ODO_OK;
+}
 
 void odo_rng_seed(odo_rng* r, uint32_t seed) {
     // glibc __srandom_r (TYPE_3): Schrage LCG fill, fptr=3, rptr=0, 310 discards

@@ -419,6 +419,28 @@ int launch_local_map_search(hipStream_t st, const LmSearch& a);
 void launch_local_map_stats(hipStream_t st, const odo_landmark* lms, const int* nkp, int kp_cap, const int32_t* slot_lm,
                             const uint8_t* pnp_mask, const odo_pair_result* pres, uint8_t* outlier,
                             odo_local_map_result* res, int nframes);
+// Matcher::Fuse's search for n_kf calls (k_fuse.hip). Device pointers: the
+// uploaded calls, keypoint rows, landmarks and index list; kp_off[k] = call
+// k's first row of bpt (n_kf + 1 prefix sums of the calls' keypoint counts),
+// rec_off[k] = its first record (prefix sums of the list lengths); bpt
+// kp_off[n_kf] sorted points, cstart n_kf x (gx * gy + 1) cell starts.
+// max_kp / max_list: the largest keypoint count / list length of a call.
+struct FuseSearch {
+    int n_kf, n_lms, max_kp, max_list;
+    const odo_fuse_kf* kfs;
+    const float *kun, *ur;
+    const uint8_t* desc;
+    const odo_landmark* lms;
+    const int32_t *lm_index, *kp_off, *rec_off;
+    LmGrid G;
+    LmCalib C;
+    float th;
+    float4* bpt;
+    int* cstart;
+    odo_fuse_cand* out;
+};
+// bins and search; -1: a call with more than 8191 keypoints
+int launch_fuse_search(hipStream_t st, const FuseSearch& a);
 void upload_adaptive_constants();
 void launch_adapt_smap(hipStream_t st, const uint8_t* pyr, size_t pyr_stride, int w, int h, int pitch, uint8_t* smap,
                        size_t smap_stride, int nframes);

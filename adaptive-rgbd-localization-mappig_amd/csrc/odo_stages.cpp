@@ -422,6 +422,102 @@ int odo_projection_match(odo_ctx* c, const float Tcw[16], const odo_landmark* lm
     return ODO_OK;
 }
 
+// Matcher::Fuse's search for every Fuse call of FuseLandmarks (k_fuse.hip):
+// validation, one upload, the bins and the search, one download.
+constexpr int FUSE_MAX_KF = 256, FUSE_MAX_KP = 8191, FUSE_MAX_LM = 65536, FUSE_MAX_REC = 1 << 20;
+int odo_fuse_search(odo_ctx* c, const odo_fuse_kf* kfs, int n_kf, const float* kun, const float* ur, const uint8_t* desc,
+                    int n_kp, const odo_landmark* lms, int n_lms, const int32_t* lm_index, int n_index, float th,
+                    odo_fuse_cand* out) {
+    if (!c || n_kf < 0 || n_kp < 0 || n_lms < 0 || n_index < 0 || (n_kf && !kfs) || (n_kp && (!kun || !ur || !desc)) ||
+        (n_lms && !lms) || (n_index && !lm_index))
+        return fail(ODO_ERR_ARG, "bad fuse_search args");
+    if (!(th >= 0.0f) || !std::isfinite(th)) return fail(ODO_ERR_ARG, "fuse_search: th must be finite and >= 0");
+    if (n_kf > FUSE_MAX_KF) return fail(ODO_ERR_CAPACITY, "fuse_search: more than 256 calls");
+    if (n_lms > FUSE_MAX_LM) return fail(ODO_ERR_CAPACITY, "fuse_search: more than 65536 landmarks");
+    std::vector<int32_t> kp_off((size_t)n_kf + 1, 0), rec_off((size_t)n_kf + 1, 0);
+    int max_kp = 0, max_list = 0;
+    for (int k = 0; k < n_kf; k++) {
+        const odo_fuse_kf& F = kfs[k];
+        if (F.kp_begin < 0 || F.kp_end < F.kp_begin || F.kp_end > n_kp)
+            return fail(ODO_ERR_ARG, "fuse_search: a keypoint range outside [0, n_kp]");
+        if (F.lm_begin < 0 || F.lm_end < F.lm_begin || F.lm_end > n_index)
+            return fail(ODO_ERR_ARG, "fuse_search: a list range outside [0, n_index]");
+        const int nk = F.kp_end - F.kp_begin, nl = F.lm_end - F.lm_begin;
+        if (nk > FUSE_MAX_KP) return fail(ODO_ERR_CAPACITY, "fuse_search: a keyframe with more than 8191 keypoints");
+        if (nl > FUSE_MAX_REC - rec_off[k]) return fail(ODO_ERR_CAPACITY, "fuse_search: more than 2^20 records");
+        kp_off[(size_t)k + 1] = kp_off[k] + nk;  // at most 256 * 8191
+        rec_off[(size_t)k + 1] = rec_off[k] + nl;
+        max_kp = std::max(max_kp, nk);
+        max_list = std::max(max_list, nl);
+    }
+    const size_t NK = (size_t)n_kf, NP = (size_t)n_kp, NR = (size_t)rec_off[NK];
+    if (NR == 0) return ODO_OK;  // no record to write
+    if (!out) return fail(ODO_ERR_ARG, "bad fuse_search args");
+    int e;
+    if ((e = sync_all(c))) return e;
+    hipStream_t st = c->stream;
+    float b[4];
+    odo_image_bounds(c, b);
+    const LmGrid G = local_map_grid(b);
+    const size_t ncells = (size_t)G.gx * G.gy;
+    Staged s;
+    const size_t o_kf = s.add(NK * sizeof(odo_fuse_kf)), o_ko = s.add((NK + 1) * 4), o_ro = s.add((NK + 1) * 4),
+                 o_kun = s.add(NP * 8), o_ur = s.add(NP * 4), o_desc = s.add(NP * 32),
+                 o_lms = s.add((size_t)n_lms * sizeof(odo_landmark)), o_idx = s.add((size_t)n_index * 4);
+    s.mark_inputs_end();
+    s.mark_outputs_begin();
+    const size_t o_out = s.add(NR * sizeof(odo_fuse_cand));
+    // on the device the sorted points and the cell starts follow the pack
+    Pack scr = s.pk;
+    const size_t o_bpt = scr.add((size_t)kp_off[NK] * sizeof(float4)), o_cs = scr.add(NK * (ncells + 1) * 4);
+    if (scr.off > c->fuse_cap) {
+        if (c->fuse_dev) (void)hipFree(c->fuse_dev);
+        c->fuse_dev = nullptr;
+        c->fuse_cap = 0;
+        const size_t cap = std::max(scr.off, (size_t)1 << 20);
+        if (hipMalloc((void**)&c->fuse_dev, cap) != hipSuccess) return fail(ODO_ERR_DEVICE, "fuse_search: hipMalloc failed");
+        c->fuse_cap = cap;
+    }
+    if ((e = s.reserve(c, c->fuse_dev))) return e;
+    memcpy(s.host<odo_fuse_kf>(o_kf), kfs, NK * sizeof(odo_fuse_kf));
+    memcpy(s.host<int32_t>(o_ko), kp_off.data(), (NK + 1) * 4);
+    memcpy(s.host<int32_t>(o_ro), rec_off.data(), (NK + 1) * 4);
+    if (n_kp) {
+        memcpy(s.host<float>(o_kun), kun, NP * 8);
+        memcpy(s.host<float>(o_ur), ur, NP * 4);
+        memcpy(s.host<uint8_t>(o_desc), desc, NP * 32);
+    }
+    if (n_lms) memcpy(s.host<odo_landmark>(o_lms), lms, (size_t)n_lms * sizeof(odo_landmark));
+    memcpy(s.host<int32_t>(o_idx), lm_index, (size_t)n_index * 4);
+    HIPCHK(s.upload(st));
+    const odo_calib& k = c->cfg.calib;
+    FuseSearch a{};
+    a.n_kf = n_kf;
+    a.n_lms = n_lms;
+    a.max_kp = max_kp;
+    a.max_list = max_list;
+    a.kfs = s.dev<odo_fuse_kf>(o_kf);
+    a.kun = s.dev<float>(o_kun);
+    a.ur = s.dev<float>(o_ur);
+    a.desc = s.dev<uint8_t>(o_desc);
+    a.lms = s.dev<odo_landmark>(o_lms);
+    a.lm_index = s.dev<int32_t>(o_idx);
+    a.kp_off = s.dev<int32_t>(o_ko);
+    a.rec_off = s.dev<int32_t>(o_ro);
+    a.G = G;
+    a.C = LmCalib{k.fx, k.fy, k.cx, k.cy, k.mbf, b[0], b[1], b[2], b[3]};
+    a.th = th;
+    a.bpt = s.dev<float4>(o_bpt);
+    a.cstart = s.dev<int>(o_cs);
+    a.out = s.dev<odo_fuse_cand>(o_out);
+    if (launch_fuse_search(st, a) != 0) return fail(ODO_ERR_CAPACITY, "fuse_search capacity");
+    HIPCHK(hipGetLastError());
+    HIPCHK(s.download(st));
+    HIPCHK(hipStreamSynchronize(st));
+    memcpy(out, s.host<odo_fuse_cand>(o_out), NR * sizeof(odo_fuse_cand));
+    return ODO_OK;
+}
+
 // Tracking::TrackLocalMap for the frames of the last batch, where they sit
 // (k_localmap.hip, then the batch's k_pnp over the gathered edges).
 constexpr int LM_MAX_LANDMARKS = 65536;

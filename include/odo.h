@@ -520,6 +520,53 @@ int odo_local_ba(odo_ctx* ctx, float* Tcw, const uint8_t* kf_fixed, int n_kf, fl
                  const odo_ba_edge* edges, int n_edges, const odo_calib* calib, const odo_ba_params* params,
                  uint8_t* edge_erase, odo_ba_result* result);
 
+/* ---- Matcher::Fuse's search (matcher.cpp:212-291) for every Fuse call of
+ * LocalMapping::FuseLandmarks (localmapping.cpp:155-180) in one launch chain.
+ * Call k is Fuse(pKF, list, th): kfs[k] names pKF's pose, its rows of the
+ * keypoint arrays and its list, entries [lm_begin, lm_end) of lm_index, each
+ * an index into lms (< 0 or >= n_lms: a null pointer). Per (call, list entry)
+ * one odo_fuse_cand record, in call order then list order:
+ *   projection  p3Dc = Rcw X + tcw as odo_projection_match computes it (double
+ *           accumulation, one rounding); z < 0.0f: ODO_FUSE_BEHIND; invz =
+ *           1 / z, x = X * invz, u = fx * x + cx (v alike), ur = u - mbf * invz,
+ *           all float; outside odo_image_bounds (u >= minX && u < maxX && v >=
+ *           minY && v < maxY fails, also for NaN): ODO_FUSE_OUTSIDE
+ *   window  KeyFrame::GetFeaturesInArea: fabsf(kp.x - u) < th && fabsf(kp.y - v)
+ *           < th (the reference passes 4.0f)
+ *   gate    u_right[j] >= 0: e2 = (ex * ex + ey * ey) + er * er, dropped when
+ *           e2 > 7.8f; otherwise e2 = ex * ex + ey * ey, dropped when e2 > 5.99f
+ *           (ex = u - kp.x, ey = v - kp.y, er = ur - u_right[j])
+ *   best    the smallest Hamming distance to lms[].desc over the gated
+ *           keypoints, the lowest keypoint index among equals (Fuse's strict
+ *           <); bestDist <= TH_LOW (50) is the caller's test
+ *   cand    the 8 lowest gated keypoint indices and n_cand, their number
+ * Only ODO_LM_BAD of lms[].flags is read. The search of one Fuse call is a
+ * function of the map at the start of the call; across the calls of
+ * FuseLandmarks' first loop only a landmark's descriptor changes (Replace's
+ * ComputeDistinctiveDescriptors), never the gated set: the caller replays the
+ * calls in order with its own map and re-scores a changed landmark's record
+ * with odo_fuse_best (DESIGN.md §4 Fuse).
+ * The call synchronises the context first (like odo_track_local_map), uploads
+ * once and downloads once; the last batch's results stay readable. n_kf == 0,
+ * n_index == 0 and empty ranges are valid. Scratch is allocated by the first
+ * call and grown by later ones; a context that never calls this allocates and
+ * launches nothing for it.
+ * ODO_ERR_ARG: a null pointer with a non-zero size, a range outside its array
+ * (or reversed), th negative or not finite; nothing is written.
+ * ODO_ERR_CAPACITY: a keyframe with more than 8191 keypoints, more than 256
+ * calls, more than 65536 landmarks, more than 2^20 records. */
+int odo_fuse_search(odo_ctx* ctx, const odo_fuse_kf* kfs, int n_kf, const float* kps_un, const float* u_right,
+                    const uint8_t* desc, int n_kp, const odo_landmark* lms, int n_lms, const int32_t* lm_index,
+                    int n_index, float th, odo_fuse_cand* out);
+/* Host only, no device: Fuse's (bestIdx, bestDist) of one record under
+ * another descriptor. kf_*: the keyframe's own kf_n rows (kp_begin is row 0).
+ * rec->n_cand <= ODO_FUSE_CANDS: over rec->cand; more: the keyframe is scanned
+ * again with the window and the gate from rec->u, v, ur. A record that was
+ * not searched or has no candidate gives (-1, INT32_MAX). ODO_ERR_ARG: a null
+ * pointer, kf_n < 0, a candidate index >= kf_n, th negative or not finite. */
+int odo_fuse_best(const odo_fuse_cand* rec, const float* kf_kps_un, const float* kf_u_right, const uint8_t* kf_desc,
+                  int kf_n, float th, const uint8_t new_desc[32], int32_t* best_idx, int32_t* best_dist);
+
 /* Kabsch::Compute (kabsch.cpp:14): one GPU workgroup (k_kabsch: centroids, A^T B
  * with a fixed-order block reduction, 3x3 Jacobi SVD). A,B: n x 3 host arrays.
  * R = W diag(1, 1, sgn(det V det W)) V^T is a rotation for every input (the

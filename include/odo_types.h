@@ -211,6 +211,32 @@ typedef struct odo_ba_result {
     int32_t pad;
 } odo_ba_result;
 
+/* One Matcher::Fuse(pKF, vpLandmarks, th) call of odo_fuse_search
+ * (matcher.cpp:212-313). 80 bytes. */
+typedef struct odo_fuse_kf {
+    float   Tcw[16];            /* pKF's pose, world -> camera, row-major */
+    int32_t kp_begin, kp_end;   /* pKF's keypoints: rows [kp_begin, kp_end) of kps_un / u_right / desc */
+    int32_t lm_begin, lm_end;   /* its list: entries [lm_begin, lm_end) of lm_index (ranges may repeat or overlap) */
+} odo_fuse_kf;
+
+#define ODO_FUSE_CANDS 8
+/* n_cand < 0: the landmark was not searched */
+#define ODO_FUSE_NULL    (-1)  /* lm_index entry < 0 or >= n_lms (a null pointer in vpLandmarks, matcher.cpp:223) */
+#define ODO_FUSE_BAD     (-2)  /* ODO_LM_BAD (matcher.cpp:225; IsInKeyFrame is the caller's, at replay) */
+#define ODO_FUSE_BEHIND  (-3)  /* p3Dc.z < 0.0f (matcher.cpp:231) */
+#define ODO_FUSE_OUTSIDE (-4)  /* !IsInImage(u, v) (matcher.cpp:241, keyframe.cpp:424-427) */
+
+/* The search of one (call, list entry) pair, in call order then list order.
+ * 40 bytes. */
+typedef struct odo_fuse_cand {
+    float    u, v, ur;              /* the projection (matcher.cpp:238-244); NaN when n_cand < 0 */
+    int32_t  n_cand;                /* keypoints inside the window that passed the gate (all of them), or ODO_FUSE_* */
+    int32_t  best_idx;              /* Fuse's bestIdx under lms[].desc: first minimum in keypoint order; -1: none */
+    int32_t  best_dist;             /* its Hamming distance; INT32_MAX: none */
+    uint16_t cand[ODO_FUSE_CANDS];  /* the first min(n_cand, 8) candidates, ascending keypoint index (relative to
+                                       kp_begin); unused entries 0xffff */
+} odo_fuse_cand;
+
 #ifdef __cplusplus
 }
 #endif

@@ -19,7 +19,8 @@ from ._abi import (DETECTOR_ADAPTIVE_FAST, DETECTOR_ADAPTIVE_ORB, DETECTOR_ORB_S
                    OrbParams, PAIR_DTYPE, PairResult, RansacParams, Rng, check, load, ptr,
                    ODOMETRY_ADAPTIVE_RBA, ODOMETRY_ADAPTIVE_RICP, ODOMETRY_RANSAC, RicpParams, RicpResult,
                    BA_EDGE_DTYPE, BA_NOTHING, BA_RAN, BaParams, BaResult,
-                   FUSE_BAD, FUSE_BEHIND, FUSE_CAND_DTYPE, FUSE_CANDS, FUSE_KF_DTYPE, FUSE_NULL, FUSE_OUTSIDE)
+                   FUSE_BAD, FUSE_BEHIND, FUSE_CAND_DTYPE, FUSE_CANDS, FUSE_KF_DTYPE, FUSE_NULL, FUSE_OUTSIDE,
+                   CLOUD_DTYPE, CLOUD_INFO_DTYPE, CLOUD_OK, CLOUD_UNFILTERED, ERR_CAPACITY)
 
 __all__ = ["Odometry", "HostFrames", "PinnedResults", "default_config", "load", "KP_DTYPE", "DMATCH_DTYPE", "PAIR_DTYPE", "rng_stream",
            "kabsch", "Calib", "OrbParams", "RansacParams", "Config", "AdaptiveParams", "DETECTOR_ORB_SLAM2",
@@ -29,7 +30,7 @@ __all__ = ["Odometry", "HostFrames", "PinnedResults", "default_config", "load", 
            "RicpParams", "RicpResult", "default_ricp_params", "LANDMARK_DTYPE", "LOCAL_MAP_DTYPE", "LocalMapResult",
            "LM_BAD", "LM_SEEN", "LM_HAS_OBS", "BA_EDGE_DTYPE", "BaParams", "BaResult", "BA_RAN", "BA_NOTHING",
            "default_ba_params", "fuse_best", "FUSE_KF_DTYPE", "FUSE_CAND_DTYPE", "FUSE_CANDS", "FUSE_NULL", "FUSE_BAD",
-           "FUSE_BEHIND", "FUSE_OUTSIDE"]
+           "FUSE_BEHIND", "FUSE_OUTSIDE", "CLOUD_DTYPE", "CLOUD_INFO_DTYPE", "CLOUD_OK", "CLOUD_UNFILTERED"]
 
 
 def default_config(width=640, height=480, max_batch=1, nfeatures=1000, iterations=200, seed=0x5EED0000,
@@ -446,6 +447,58 @@ class Odometry:
         check(self.lib.odo_fuse_search(self.h, ptr(K), len(K), ptr(kun), ptr(ur), ptr(desc), row, ptr(lms), len(lms),
                                        ptr(idx), len(idx), th, ptr(out)))
         return out
+
+    def _twc(self, Twc, n):
+        if Twc is None:
+            return None
+        T = np.ascontiguousarray(Twc, np.float32).reshape(-1, 16)
+        if len(T) != n:
+            raise ValueError(f"Twc: {len(T)} matrices for {n} frames")
+        return T
+
+    def dense_clouds(self, bgr_ptr: int, depth_ptr: int, n: int, leaf: float = 0.03, Twc=None):
+        """odo_dense_clouds: Frame::CreateCloud + VoxelGridFilterCloud(leaf)
+        (frame.cpp:191-226; leaf 0: CreateCloud alone) and the optional map
+        transform Twc (n x 4 x 4) for n device-resident frames laid out as
+        track_batch's. Returns the CLOUD_INFO_DTYPE records; the points stay on
+        the device (get_dense_cloud, dense_cloud_device)."""
+        info = np.zeros(n, CLOUD_INFO_DTYPE)
+        T = self._twc(Twc, n)
+        check(self.lib.odo_dense_clouds(self.h, C.c_void_p(bgr_ptr), C.c_void_p(depth_ptr), n, leaf, ptr(T), ptr(info)))
+        return info
+
+    def dense_clouds_host(self, bgr, depth, leaf: float = 0.03, Twc=None):
+        """odo_dense_clouds_host: dense_clouds on host frames (n x H x W x 3 u8,
+        n x H x W u16). Returns the infos."""
+        bgr = np.ascontiguousarray(bgr, np.uint8)
+        depth = np.ascontiguousarray(depth, np.uint16)
+        W, H = self.cfg.width, self.cfg.height
+        n = bgr.shape[0]
+        if bgr.shape != (n, H, W, 3) or depth.shape != (n, H, W):
+            raise ValueError(f"expected bgr {(n, H, W, 3)} and depth {(n, H, W)}, got {bgr.shape} and {depth.shape}")
+        info = np.zeros(n, CLOUD_INFO_DTYPE)
+        T = self._twc(Twc, n)
+        check(self.lib.odo_dense_clouds_host(self.h, ptr(bgr), ptr(depth), n, leaf, ptr(T), ptr(info)))
+        return info
+
+    def get_dense_cloud(self, i: int, counts: bool = False):
+        """odo_get_dense_cloud: frame i of the last dense_clouds call as a
+        CLOUD_DTYPE array; with counts=True (points, voxel populations)."""
+        n = C.c_int(0)
+        rc = self.lib.odo_get_dense_cloud(self.h, i, None, None, 0, C.byref(n))
+        if rc not in (0, ERR_CAPACITY):
+            check(rc)
+        pts = np.zeros(n.value, CLOUD_DTYPE)
+        cnt = np.zeros(n.value, np.int32) if counts else None
+        check(self.lib.odo_get_dense_cloud(self.h, i, ptr(pts), ptr(cnt), n.value, C.byref(n)))
+        return (pts, cnt) if counts else pts
+
+    def dense_cloud_device(self, i: int):
+        """odo_dense_cloud_device: (points pointer, counts pointer, n) of frame
+        i where it lies in HBM, valid until the next dense-cloud call."""
+        dp, dc, n = C.c_void_p(0), C.c_void_p(0), C.c_int(0)
+        check(self.lib.odo_dense_cloud_device(self.h, i, C.byref(dp), C.byref(dc), C.byref(n)))
+        return dp.value or 0, dc.value or 0, n.value
 
     def local_map(self, i: int):
         """odo_get_local_map: frame i of the last track_local_map. Returns

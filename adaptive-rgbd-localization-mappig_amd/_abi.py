@@ -99,7 +99,14 @@ class BaResult(C.Structure):
                 ("n_erase", C.c_int32), ("n_level1", C.c_int32), ("status", C.c_int32), ("pad", C.c_int32)]
 
 
+class CloudInfo(C.Structure):
+    """odo_cloud_info (include/odo_types.h)."""
+    _fields_ = [("status", C.c_int32), ("n_valid", C.c_int32), ("n_points", C.c_int32), ("min_b", C.c_int32 * 3),
+                ("div_b", C.c_int32 * 3), ("min_p", C.c_float * 3), ("max_p", C.c_float * 3)]
+
+
 BA_RAN, BA_NOTHING = 0, 1  # include/odo_types.h ODO_BA_*
+CLOUD_OK, CLOUD_UNFILTERED = 0, 1  # include/odo_types.h ODO_CLOUD_*
 ODOMETRY_ADAPTIVE_RBA = 0   # include/odo.h ODO_ODOMETRY_ADAPTIVE_RBA
 ODOMETRY_RANSAC = 1         # include/odo.h ODO_ODOMETRY_RANSAC
 ODOMETRY_ADAPTIVE_RICP = 2  # include/odo.h ODO_ODOMETRY_ADAPTIVE_RICP
@@ -155,6 +162,10 @@ FUSE_CANDS = 8  # include/odo_types.h ODO_FUSE_CANDS
 FUSE_CAND_DTYPE = np.dtype([("u", "<f4"), ("v", "<f4"), ("ur", "<f4"), ("n_cand", "<i4"), ("best_idx", "<i4"),
                             ("best_dist", "<i4"), ("cand", "<u2", FUSE_CANDS)])  # odo_fuse_cand
 FUSE_NULL, FUSE_BAD, FUSE_BEHIND, FUSE_OUTSIDE = -1, -2, -3, -4  # include/odo_types.h ODO_FUSE_*
+CLOUD_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("b", "u1"), ("g", "u1"), ("r", "u1"),
+                        ("a", "u1")])  # odo_cloud_point
+CLOUD_INFO_DTYPE = np.dtype([("status", "<i4"), ("n_valid", "<i4"), ("n_points", "<i4"), ("min_b", "<i4", 3),
+                             ("div_b", "<i4", 3), ("min_p", "<f4", 3), ("max_p", "<f4", 3)])  # odo_cloud_info
 
 # Every symbol include/odo.h declares, with its ctypes signature.
 SIGNATURES = {
@@ -219,6 +230,10 @@ SIGNATURES = {
     "odo_kp_capacity": (C.c_int, [P]),
     "odo_fuse_search": (C.c_int, [P, P, C.c_int, P, P, P, C.c_int, P, C.c_int, P, C.c_int, C.c_float, P]),
     "odo_fuse_best": (C.c_int, [P, P, P, P, C.c_int, C.c_float, P, P, P]),
+    "odo_dense_clouds": (C.c_int, [P, P, P, C.c_int, C.c_float, P, P]),
+    "odo_dense_clouds_host": (C.c_int, [P, P, P, C.c_int, C.c_float, P, P]),
+    "odo_get_dense_cloud": (C.c_int, [P, C.c_int, P, P, C.c_int, P]),
+    "odo_dense_cloud_device": (C.c_int, [P, C.c_int, P, P, P]),
     "odo_default_ba_params": (None, [P]),
     "odo_local_ba": (C.c_int, [P, P, P, C.c_int, P, C.c_int, P, C.c_int, P, P, P, P]),
     "odo_ransac_hyps": (C.c_int, [P, P, C.c_int, P, C.c_int, P, C.c_int, P, P, P, C.c_int, C.c_int, P, P]),

@@ -1,8 +1,9 @@
 // The context behind the C-ABI (include/odo.h) and what its host translation
 // units share: odo_capi.cpp (lifetime, setters, getters), odo_geometry.cpp
 // (host tables), odo_batch.cpp (the pipelined path), odo_stages.cpp (the
-// synchronous per-stage entry points), odo_hyps.cpp (single-pair RANSAC) and
-// odo_host.cpp (no device). Host only: no kernel file includes it.
+// synchronous per-stage entry points), odo_cloud.cpp (dense clouds),
+// odo_hyps.cpp (single-pair RANSAC) and odo_host.cpp (no device). Host only:
+// no kernel file includes it.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -302,6 +303,15 @@ struct odo_ctx {
     // starts), allocated by its first call and regrown when a call needs more
     uint8_t* fuse_dev = nullptr;
     size_t fuse_cap = 0;
+    // odo_dense_clouds: the scratch block (plans, histograms, the (key, pixel)
+    // ping-pong of every frame of a call) and the output block (the points,
+    // then their counts at cloud_counts_at), each allocated by the first call
+    // and regrown when a call needs more. cloud_n: the frames of the last call
+    // (-1: none), cloud_off / cloud_np their first point and point count
+    uint8_t *cloud_dev = nullptr, *cloud_out = nullptr;
+    size_t cloud_cap = 0, cloud_out_cap = 0, cloud_counts_at = 0;
+    int cloud_n = -1;
+    std::vector<int32_t> cloud_off, cloud_np;
     // sequence state: the last tracked batch sits in frame set seq_set (its
     // last frame at slot seq_n); getters read view_set / view_n
     bool has_prev = false;
@@ -401,7 +411,7 @@ inline FrameSlot frame_at(const odo_ctx* c, size_t slot) {
 // odo_set_timing: timing events serialise the queue they sit on, which costs
 // tens of microseconds per mark once several streams are busy.
 inline void tmark(odo_ctx* c, int i, hipStream_t st) {
-    if (c->timing) hipEventRecord(c->ev[i], st);
+    if (c->timing) (void)hipEventRecord(c->ev[i], st);
 }
 
 // Packed layout in the staging buffer: 256-byte aligned sections
@@ -434,6 +444,7 @@ int run_extract(odo_ctx* c, int set, const uint8_t* d_bgr, const uint16_t* d_dep
                 bool geometry = true);         // odo_batch.cpp
 void launch_set_knn2(odo_ctx* c, hipStream_t st, int s, int n);
 void free_local_map(odo_ctx* c);               // odo_stages.cpp
+void free_dense_clouds(odo_ctx* c);            // odo_cloud.cpp
 void free_hyp_session(HypSession* h);          // odo_hyps.cpp
 
 // One packed round trip of a synchronous entry point. The sections are laid

@@ -441,6 +441,41 @@ struct FuseSearch {
 };
 // bins and search; -1: a call with more than 8191 keypoints
 int launch_fuse_search(hipStream_t st, const FuseSearch& a);
+// Dense clouds (k_cloud.hip). A frame's elements (pixels, then its valid
+// points) are cut into chunks of CLOUD_CHUNK, one wave each; nch chunks cover
+// the W * H pixels of a frame.
+constexpr int CLOUD_CHUNK = 1024;
+// the plan of one frame, written by k_cloud_bounds / k_cloud_plan / k_cloud_voxels
+struct CloudFrame {
+    uint32_t lo[3], hi[3];  // min / max of x, y, z as order-preserving bits
+    int32_t n_valid;        // pixels with z > 0
+    int32_t filtered;       // the voxel grid applies (else the raster cloud is the result)
+    int32_t npass;          // radix passes (key bytes that can be non-zero); the sorted keys lie in buffer npass & 1
+    float inv;              // 1.0f / leaf
+    int32_t min_b[3];
+    uint32_t div0, div01;   // div_b[0], div_b[0] * div_b[1] (wrapping)
+    int32_t n_points, out_off;  // voxels; the frame's first point in the output
+    int32_t pad;
+};
+struct CloudArgs {
+    int n, W, H, nch;
+    FrameCalib cal;
+    float leaf;
+    const uint8_t* bgr;     // [n][H][W][3]
+    const uint16_t* depth;  // [n][H][W]
+    const float* Twc;       // [n][16] or nullptr
+    CloudFrame* fr;         // [n]
+    odo_cloud_info* info;   // [n]
+    int32_t *chunk_off, *head_off;  // [n][nch]: valid pixels / voxel heads before each chunk
+    int32_t* hist;          // [n][nch][256]
+    uint32_t *key[2], *idx[2];  // [n][W * H] each: (key, pixel) ping-pong
+    odo_cloud_point* out;
+    int32_t* counts;
+};
+// bounds, plan, keys, the radix sort, the voxel heads and info[] (all but the points)
+void launch_cloud_voxels(hipStream_t st, const CloudArgs& a);
+// the voxel starts and the centroids into out / counts; max_points: the largest n_points of a frame
+void launch_cloud_points(hipStream_t st, const CloudArgs& a, int max_points);
 void upload_adaptive_constants();
 void launch_adapt_smap(hipStream_t st, const uint8_t* pyr, size_t pyr_stride, int w, int h, int pitch, uint8_t* smap,
                        size_t smap_stride, int nframes);

@@ -567,6 +567,60 @@ int odo_fuse_search(odo_ctx* ctx, const odo_fuse_kf* kfs, int n_kf, const float*
 int odo_fuse_best(const odo_fuse_cand* rec, const float* kf_kps_un, const float* kf_u_right, const uint8_t* kf_desc,
                   int kf_n, float th, const uint8_t new_desc[32], int32_t* best_idx, int32_t* best_dist);
 
+/* ---- Dense clouds: Frame::CreateCloud (frame.cpp:191-215), then
+ * Frame::VoxelGridFilterCloud(leaf) (frame.cpp:217-226, pcl::VoxelGrid
+ * <PointXYZRGB>), then pcl::transformPointCloud(cloud, Twc) (Tests/
+ * Draw_map_pose.cpp:72-73, 99-103; Tests/GICP_test.cpp:66-67), for n frames
+ * already in HBM (laid out as odo_track_batch's) in one launch chain. PCL is
+ * restated, not linked (DESIGN.md §2 Dense clouds):
+ *   CreateCloud  z = (float)d16 * depth_factor; pixel (row i, column j) kept
+ *           iff z > 0, raster order; x = ((float)j - cx) * z * invfx, y =
+ *           ((float)i - cy) * z * invfy (invfx the float 1.0f / fx), b, g, r
+ *           from the frame, a = 255. No undistortion, as in the reference.
+ *   leaf == 0  CreateCloud alone: ODO_CLOUD_UNFILTERED, every count 1.
+ *   VoxelGrid  inv = 1.0f / leaf; min_p / max_p the exact per-axis min / max;
+ *           d[a] = (int64)((max_p[a] - min_p[a]) * inv) + 1; d0 * d1 * d2 >
+ *           INT32_MAX (or a product / floor outside the integer's range, which
+ *           PCL leaves undefined): the input cloud, ODO_CLOUD_UNFILTERED. Else
+ *           min_b = (int)floorf(min_p * inv), max_b alike, div_b = max_b - min_b
+ *           + 1; per point ijk[a] = (int)(floorf(p[a] * inv) - (float)min_b[a]),
+ *           key = ijk0 + ijk1 * div_b[0] + ijk2 * (div_b[0] * div_b[1]) in
+ *           wrapping 32-bit arithmetic read as unsigned; one output point per
+ *           distinct key, ascending.
+ *   centroid  count points; b, g, r, a each (uint8)(uint32)((float)sum /
+ *           (float)count) with the exact integer sum; x, y, z a float sum in a
+ *           fixed order (bit-identical run to run) divided by (float)count.
+ *   Twc     row-major 4 x 4 per frame (the inverse of the caller's Tcw), or
+ *           NULL; applied to the result: x' = ((m00 * x + m01 * y) + m02 * z) +
+ *           m03 in float, rows 1 and 2 alike; colours untouched.
+ *   n_valid == 0  n_points 0, ODO_CLOUD_OK, the info's bounds zero (PCL is
+ *           undefined on an empty cloud).
+ * The call synchronises the context first (like odo_track_local_map), runs on
+ * odo_stream() and returns with info[0..n) filled; the points stay in HBM,
+ * compact, frame after frame. The last batch's results stay readable. Scratch
+ * is allocated by the first call and grown by later ones; a context that
+ * never calls this allocates and launches nothing for it.
+ * ODO_ERR_ARG: a null pointer, n outside 1..max_batch, leaf negative or not
+ * finite, a non-finite Twc entry; nothing is written. */
+int odo_dense_clouds(odo_ctx* ctx, const uint8_t* d_bgr, const uint16_t* d_depth, int n, float leaf, const float* Twc,
+                     odo_cloud_info* info);
+/* The same from host frames (frame.cpp:191-226 on the caller's images): one
+ * upload through the context's input staging, then odo_dense_clouds. */
+int odo_dense_clouds_host(odo_ctx* ctx, const uint8_t* bgr, const uint16_t* depth, int n, float leaf, const float* Twc,
+                          odo_cloud_info* info);
+/* Frame i of the last dense-cloud call (KeyFrame's mpCloud, keyframe.cpp:46-47):
+ * up to cap points into pts and, when counts is not NULL, each point's voxel
+ * population into counts; *n is the cloud's point count. A cloud of more than
+ * cap points: ODO_ERR_CAPACITY after the first cap were copied.
+ * ODO_ERR_STATE before any dense-cloud call; ODO_ERR_ARG: i outside the last
+ * call's frames, cap < 0, a null pts with cap > 0, a null n. */
+int odo_get_dense_cloud(odo_ctx* ctx, int i, odo_cloud_point* pts, int32_t* counts, int cap, int* n);
+/* The same buffers where they lie in HBM (what a device-side
+ * GeneralizedICP::Compute(pF1, pF2, guess), generalizedicp.cpp:41-53, would
+ * read), valid until the next dense-cloud call or odo_destroy. d_counts may be
+ * NULL. Errors as odo_get_dense_cloud. */
+int odo_dense_cloud_device(odo_ctx* ctx, int i, const odo_cloud_point** d_pts, const int32_t** d_counts, int* n);
+
 /* Kabsch::Compute (kabsch.cpp:14): one GPU workgroup (k_kabsch: centroids, A^T B
  * with a fixed-order block reduction, 3x3 Jacobi SVD). A,B: n x 3 host arrays.
  * R = W diag(1, 1, sgn(det V det W)) V^T is a rotation for every input (the

@@ -303,6 +303,26 @@ public:
         mvbOutlier.assign(N, false);
     }
 
+    // Frame::CreateCloud (frame.cpp:191-215): one point per pixel with depth,
+    // raster order, on the device (odo_dense_clouds_host at leaf 0). A frame
+    // that has a cloud keeps it, as the reference's `if (mpCloud) return`.
+    void CreateCloud() {
+        if (mbCloud) return;
+        DenseCloud(0.0f);
+        mbCloud = true;
+    }
+    // Frame::VoxelGridFilterCloud (frame.cpp:217-226): without a cloud it
+    // returns (frame.cpp:219). The mirror's one difference: the filter runs on
+    // the frame's images (CreateCloud and the voxel grid in one device call),
+    // so calling it twice filters the images again at the new leaf, where PCL
+    // would filter the filtered cloud.
+    void VoxelGridFilterCloud(float resolution) {
+        if (!mbCloud) return;
+        DenseCloud(resolution);
+    }
+    bool HasCloud() const { return mbCloud; }
+    std::vector<odo_cloud_point> mpCloud;  // frame.h:80 (DenseCloud::Ptr): the points, camera frame
+
     int Width() const { return mW; }
     int Height() const { return mH; }
     void SetPose(const Pose& Tcw) { mTcw = Tcw; }
@@ -341,6 +361,17 @@ public:
     const uint16_t* ImDepth() const { return mImDepth; }
 
 private:
+    void DenseCloud(float leaf) {
+        mpCloud.clear();
+        if (!mImDepth) return;  // no depth image: no pixel has z > 0
+        odo_ctx* c = detail::geometry_ctx(mW, mH);
+        odo_cloud_info info;
+        Check(odo_dense_clouds_host(c, mImColor, mImDepth, 1, leaf, nullptr, &info), "Frame::CreateCloud");
+        mpCloud.resize((size_t)info.n_points);
+        int n = 0;
+        Check(odo_get_dense_cloud(c, 0, mpCloud.data(), nullptr, info.n_points, &n), "Frame::CreateCloud");
+    }
+    bool mbCloud = false;
     int mW, mH;
     const uint8_t* mImColor = nullptr;   // BGR8: the frame's copy, or the caller's (BorrowImages)
     const uint16_t* mImDepth = nullptr;  // depth16 (or null), likewise

@@ -237,6 +237,25 @@ typedef struct odo_fuse_cand {
                                        kp_begin); unused entries 0xffff */
 } odo_fuse_cand;
 
+/* One point of a dense cloud (odo_dense_clouds): pcl::PointXYZRGB's payload,
+ * camera frame (or the frame Twc maps to). 16 bytes. */
+typedef struct odo_cloud_point {
+    float   x, y, z;
+    uint8_t b, g, r, a;         /* a = 255 for a CreateCloud point (PCL's default), the voxel's mean like b, g, r */
+} odo_cloud_point;
+
+#define ODO_CLOUD_OK         0  /* the voxel grid filter ran (or the cloud is empty) */
+#define ODO_CLOUD_UNFILTERED 1  /* leaf == 0, or VoxelGrid's "leaf size is too small" return: CreateCloud's points */
+
+/* One frame of odo_dense_clouds. 60 bytes. */
+typedef struct odo_cloud_info {
+    int32_t status;             /* ODO_CLOUD_* */
+    int32_t n_valid;            /* CreateCloud's points: pixels with z > 0 */
+    int32_t n_points;           /* points of the result */
+    int32_t min_b[3], div_b[3]; /* VoxelGrid's min_b_ / div_b_ (zero when unfiltered or empty) */
+    float   min_p[3], max_p[3]; /* getMinMax3D of CreateCloud's points, before Twc (zero when empty) */
+} odo_cloud_info;
+
 #ifdef __cplusplus
 }
 #endif

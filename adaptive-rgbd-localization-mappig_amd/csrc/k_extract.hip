@@ -204,8 +204,23 @@ __global__ void __launch_bounds__(FS_TH) k_fast_seg(const uint8_t* __restrict__ 
                                                    uint32_t* __restrict__ cand, int* __restrict__ cand_cnt, int ncells,
                                                    int cell_cap, int ini_th, int min_th, FastLds LO) {
     EXTRACT_PRIO();
+#ifndef FS_FREE_VGPRS
+    // Keeps the kernel's register allocation at 80 per lane, where it was
+    // until round 10 (the code needs 63): at 64 more segment workgroups fit
+    // on a CU beside the pair stream's waves, and the hard workload, whose
+    // step is the pair chain, lost 1-2 % (k_fast_seg, round 10)
+    asm volatile("" ::: "v79");
+#endif
     extern __shared__ __attribute__((aligned(16))) uint8_t fs_lds[];
-    const FastSeg G = segs[blockIdx.x];
+    // the segment's table entry as two 16-byte loads at a uniform address
+    // (scalar loads; its 16-bit fields read one by one went through the
+    // vector memory path)
+    FastSeg G;
+    {
+        const uint4* const gp = reinterpret_cast<const uint4*>(segs + blockIdx.x);
+        const uint4 g2[2] = {gp[0], gp[1]};
+        __builtin_memcpy(&G, g2, sizeof(G));
+    }
     const int f = blockIdx.y;
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     uint8_t* const roi = fs_lds;
@@ -222,16 +237,30 @@ __global__ void __launch_bounds__(FS_TH) k_fast_seg(const uint8_t* __restrict__ 
     constexpr int RS = FS_RS, RS4 = RS >> 2;
     const int sh = G.x0 & 15;  // staged from the 16-byte column below x0: pixel (r, x) at byte r*RS + sh + x
     {
-        const uint4* src = reinterpret_cast<const uint4*>(pyr + (size_t)f * pyr_stride + L.off +
-                                                          (size_t)G.y0 * L.pitch + (G.x0 & ~15));
-        const int nw = (sh + cols + 15) >> 4, p16 = L.pitch >> 4;
-        const int rstep = FS_TH / nw, k = t % nw, r0 = t / nw;
-        if (r0 < rstep)
-            for (int r = r0; r < R; r += rstep)
-                reinterpret_cast<uint4*>(roi + r * RS)[k] = src[__umul24((uint32_t)r, (uint32_t)p16) + (uint32_t)k];
+        // thread t stages 16-byte column k = t % nw of rows t / nw, + rstep, ...:
+        // the grid (nw, rstep = FS_TH / nw, t / nw by a multiply) comes from
+        // the host table, and a row's address is a 32-bit byte offset from the
+        // segment's uniform base (three run-time divisions and 64-bit address
+        // arithmetic per workgroup until round 10)
+        static_assert(FS_TH == 256, "fast_seg_staging sizes the grid for 256 threads");
+        const uint8_t* const src = pyr + (size_t)f * pyr_stride + L.off + (size_t)G.y0 * L.pitch + (G.x0 & ~15);
+        const uint32_t nw = (uint32_t)G.nw, rstep = (uint32_t)G.rstep, pitch = (uint32_t)L.pitch;
+        const uint32_t r0 = __umul24((uint32_t)t, (uint32_t)G.rmag) >> 12, k = (uint32_t)t - __umul24(r0, nw);
+        if (r0 < rstep) {
+            uint32_t so = __umul24(r0, pitch) + 16u * k, lo = __umul24(r0, (uint32_t)RS) + 16u * k;
+            const uint32_t sstep = __umul24(rstep, pitch), lstep = __umul24(rstep, (uint32_t)RS);
+            for (uint32_t r = r0; r < (uint32_t)R; r += rstep, so += sstep, lo += lstep)
+                *reinterpret_cast<uint4*>(roi + lo) = *reinterpret_cast<const uint4*>(src + so);
+        }
         for (int i = t; i < (R * RS) >> 4; i += FS_TH) reinterpret_cast<uint4*>(score)[i] = uint4{0, 0, 0, 0};
-        for (int i = t; i < R * BW; i += FS_TH) bits[i] = 0;
-        for (int i = t; i < R * FS_NCM; i += FS_TH) cnt[i] = 0;
+        // the kept bitmap and the counts lie back to back (fast_lds_plan, both
+        // 16-byte aligned): one clear, 16 bytes per store, up to the segment's
+        // last count
+        {
+            uint4* const z = reinterpret_cast<uint4*>(bits);
+            const int nz = (LO.cnt - LO.bits + R * FS_NCM * 4 + 15) >> 4;
+            for (int i = t; i < nz; i += FS_TH) z[i] = uint4{0, 0, 0, 0};
+        }
         if (t == 0) M.ncl = 0, M.ovf = 0;
     }
     const int drows = R - 6;
@@ -246,7 +275,7 @@ __global__ void __launch_bounds__(FS_TH) k_fast_seg(const uint8_t* __restrict__ 
         }
     }
     __syncthreads();
-    const float inv_w = 1.0f / (float)wcell;
+    const float inv_w = G.inv_w;
     uint32_t* const out = cand + ((size_t)f * ncells + G.ci0) * cell_cap;
     typedef short s16x2 __attribute__((ext_vector_type(2)));
     for (int pass = 0; pass < 2; pass++) {
@@ -259,8 +288,12 @@ __global__ void __launch_bounds__(FS_TH) k_fast_seg(const uint8_t* __restrict__ 
         {
             const s16x2 thv = {(short)thc, (short)thc};
             // item it = (detection row ii, quad kk): ii = (it + 0.5) / NL in
-            // float (it < 2^13, so the error stays far below the 0.5 / NL margin)
-            const float inl = NL > 0 ? 1.0f / (float)NL : 0.0f, inl_h = 0.5f * inl;
+            // float (it < 2^13, so the error stays far below the 0.5 / NL margin:
+            // ii <= 64 and NL <= FS_RS / 4 + FS_NCM put the margin at 2^-8 and
+            // the error of the 1-ulp v_rcp_f32 plus the fma's rounding below
+            // 2^-16, so the hardware reciprocal gives the quotient of the
+            // 12-instruction IEEE division it replaces)
+            const float inl = NL > 0 ? __builtin_amdgcn_rcpf((float)NL) : 0.0f, inl_h = 0.5f * inl;
             int head = 0, tail = 0;
             // segment test + cornerScore of ring entries [h, h + n), two per lane
             auto seg_test = [&](int h, int n) {
@@ -416,8 +449,12 @@ __global__ void __launch_bounds__(FS_TH) k_fast_seg(const uint8_t* __restrict__ 
         // corner at ROI byte offset o -> (row, segment x, cell) and its cell's
         // detection columns [xl, xh) in segment x
         auto locate = [&](int o, int& r, int& xs, int& jl, int& xl, int& xh) {
-            r = o / RS;
-            xs = (o - r * RS) - sh;
+            // o / RS for o < 2^16 (a 24-bit multiply: 61681 * 272 = 2^24 + 16)
+            if constexpr (RS == 272)
+                r = (int)(__umul24((uint32_t)o, 61681u) >> 24);
+            else
+                r = o / RS;
+            xs = (o - __mul24(r, RS)) - sh;
             jl = (int)(((float)(xs - 3) + 0.5f) * inv_w);
             xl = 3 + jl * wcell;
             xh = min(xl + wcell, cols - 3);
@@ -462,12 +499,7 @@ __global__ void __launch_bounds__(FS_TH) k_fast_seg(const uint8_t* __restrict__ 
             if (pass == 1 && !M.retry[j]) continue;  // uniform per wave
             const int r = 3 + lane;
             const int v = lane < drows ? cnt[r * FS_NCM + j] : 0;
-            int incl = v;
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const int y = __shfl_up(incl, o);
-                if (lane >= o) incl += y;
-            }
+            const int incl = wave_incl_scan(v);
             if (lane < drows) cnt[r * FS_NCM + j] = incl - v;
             if (lane == 63) M.tot[j] = incl;
         }
@@ -499,37 +531,39 @@ __global__ void __launch_bounds__(FS_TH) k_fast_seg(const uint8_t* __restrict__ 
             scan(place);
         // ---- cells that kept nothing: their quads, for the minThFAST pass
         if (pass == 0) {
-            if (t < nc) M.retry[t] = M.tot[t] == 0;
-            __syncthreads();
-            if (t < nc && M.retry[t]) FS_STAT(6, 1);
-            if (t == 0) FS_STAT(7, nc);
-            if (t < nc) {
-                const int xa = sh + 3 + t * wcell, xe = sh + min(3 + (t + 1) * wcell, cols - 3);
-                if (M.retry[t]) {
-                    int at = 0;  // entries of the retry cells before this one
-                    for (int j = 0; j < t; j++)
-                        if (M.retry[j]) {
-                            const int ja = sh + 3 + j * wcell, je = sh + min(3 + (j + 1) * wcell, cols - 3);
-                            at += ((je - 1) >> 2) - (ja >> 2) + 1;
+            // One wave, a lane per cell: a retry cell's first qlist entry is the
+            // exclusive prefix of the retry cells' quad counts and the total is
+            // the next pass's row length (serial loops over the cells, per thread
+            // and on thread 0, until round 10). Placement by the list reads
+            // nothing written here; by the score map (scan) it reads qlist, so
+            // only that path waits for every wave's placement first.
+            if (ovf) __syncthreads();
+            if (wave == 0) {
+                // (the asm pins the cell arithmetic here: hoisted out of the pass
+                // loop it ran in every wave before the first barrier)
+                int lane = t;
+                asm volatile("" : "+v"(lane));
+                const bool cell = lane < nc;
+                const int tot = cell ? M.tot[lane] : 1;
+                const bool rt = tot == 0;
+                const int xa = sh + 3 + lane * wcell, xe = sh + min(3 + (lane + 1) * wcell, cols - 3);
+                const int nq = rt ? ((xe - 1) >> 2) - (xa >> 2) + 1 : 0;
+                const int incl = wave_incl_scan(nq);
+                if (lane == 0) FS_STAT(7, nc);
+                if (cell) {
+                    M.retry[lane] = rt;
+                    if (rt) {
+                        FS_STAT(6, 1);
+                        int at = incl - nq;
+                        for (int m = xa >> 2; m <= (xe - 1) >> 2; m++) {
+                            const int lo = max(xa - 4 * m, 0), hi = min(xe - 4 * m, 4);
+                            qlist[at++] = uint2{fs_msb_mask((0xFu << lo) & ((1u << hi) - 1u)), 4u * (uint32_t)m};
                         }
-                    for (int m = xa >> 2; m <= (xe - 1) >> 2; m++) {
-                        const int lo = max(xa - 4 * m, 0), hi = min(xe - 4 * m, 4);
-                        qlist[at++] = uint2{fs_msb_mask((0xFu << lo) & ((1u << hi) - 1u)), 4u * (uint32_t)m};
+                    } else {
+                        cand_cnt[(size_t)f * ncells + G.ci0 + lane] = min(tot, cell_cap);
                     }
-                } else {
-                    cand_cnt[(size_t)f * ncells + G.ci0 + t] = min(M.tot[t], cell_cap);
                 }
-            }
-            if (t == 0) {
-                int n = 0;
-                for (int j = 0; j < nc; j++)
-                    if (M.retry[j]) {
-                        const int ja = sh + 3 + j * wcell, je = sh + min(3 + (j + 1) * wcell, cols - 3);
-                        n += ((je - 1) >> 2) - (ja >> 2) + 1;
-                    }
-                M.nl = n;
-                M.ncl = 0;
-                M.ovf = 0;
+                if (lane == 63) M.nl = incl, M.ncl = 0, M.ovf = 0;
             }
             __syncthreads();
             if (M.nl == 0) return;  // uniform: no cell to retry

@@ -26,14 +26,32 @@ namespace odo {
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
-// ORB_SLAM2 pattern test t: (x0, y0, x1, y1). No kernel reads it any more; it
-// stays because dropping it moves c_pat8 and with it the addresses in
-// k_finalize_lds's text, which belongs to a change that may alter device code
-__constant__ float4 c_patf[256];
-// the same tests as signed bytes, lane-major: c_pat8[s * 16 + w] = test w * 16 + s
-// (k_finalize_lds lane s's sixteen tests in 64 contiguous bytes)
+// ORB_SLAM2 pattern test t = (x0, y0, x1, y1) as signed bytes, lane-major:
+// c_pat8[s * 16 + w] = test w * 16 + s (k_finalize_lds lane s's sixteen tests
+// in 64 contiguous bytes)
 __constant__ uint32_t c_pat8[256];
-__constant__ int c_umax16[16];    // IC_Angle disc half-widths per |v|
+// IC_Angle disc masks: row |v|'s dword i has byte bb set (0xff) where column
+// u = 4 i + bb - 15 lies inside the disc, |u| <= umax[|v|]. A compile-time
+// table: every workgroup copies it to LDS with one load per thread (until
+// round 10 each rebuilt it from the half-widths, ~27 VALU per wave)
+struct DiscTab {
+    uint32_t m[16 * 8];
+};
+constexpr DiscTab make_disc_tab() {
+    constexpr int umax[16] = {15, 15, 15, 15, 14, 14, 14, 13, 13, 12, 11, 10, 9, 8, 6, 3};
+    DiscTab T{};
+    for (int av = 0; av < 16; av++)
+        for (int i = 0; i < 8; i++) {
+            uint32_t m = 0;
+            for (int bb = 0; bb < 4; bb++) {
+                const int u = 4 * i + bb - 15;
+                if (u >= -umax[av] && u <= umax[av]) m |= 0xffu << (8 * bb);
+            }
+            T.m[av * 8 + i] = m;
+        }
+    return T;
+}
+__constant__ DiscTab c_disc = make_disc_tab();
 
 // 1.5 * 2^23: for |x| < 2^22, the float sum x + RND_MAGIC is x rounded half to
 // even (cvRound) plus the magic, so its low mantissa bits are the integer.
@@ -70,52 +88,64 @@ __global__ void __launch_bounds__(64 * NW) k_finalize_lds(const uint8_t* __restr
                                                       size_t pyr_stride, const LevelDesc* __restrict__ lv, int nlevels,
                                                       const uint32_t* __restrict__ okp, const int* __restrict__ ocnt,
                                                       int okp_stride, orb_kp* __restrict__ kps, uint8_t* __restrict__ desc,
-                                                      int* __restrict__ nkp, int kp_cap) {
+                                                      int* __restrict__ nkp, int kp_cap, uint32_t gx_rcp) {
     if (ODO_EXTRACT_PRIO) __builtin_amdgcn_s_setprio(ODO_EXTRACT_PRIO);
     __shared__ uint64_t s_bal[NW][16];
     // disc masks, rows padded to 12 dwords: the 16 lanes of a ds_read_b128
     // group read 16 different rows, which at 8 dwords met on 2 banks each
     __shared__ __attribute__((aligned(16))) uint32_t s_disc[16][12];
     __shared__ __attribute__((aligned(16))) uint32_t s_patch[NW * FIN_KPW][FL_KP_DW];
-    for (int d = threadIdx.x; d < 128; d += 64 * NW) {
-        const int av = d >> 3, i = d & 7;
-        const int um = c_umax16[av];
-        uint32_t m = 0;
-#pragma unroll
-        for (int bb = 0; bb < 4; bb++) {
-            const int u = 4 * i + bb - 15;
-            if (u >= -um && u <= um) m |= 0xffu << (8 * bb);
-        }
-        s_disc[av][i] = m;
-    }
+    for (int d = threadIdx.x; d < 128; d += 64 * NW) s_disc[d >> 3][d & 7] = c_disc.m[d];
+    // XCD remap (workgroup h runs on XCD h & 7: the eight XCDs take eight
+    // contiguous runs of the (frame, block) list). gx_rcp = ceil(2^32 /
+    // gridDim.x) from the host, exact for lid * gridDim.x < 2^32 (0: no
+    // remap): the whole index computation stays on the scalar unit
     int bx = blockIdx.x, f = blockIdx.y;
     {
-        const int total = gridDim.x * gridDim.y;
-        if ((total & 7) == 0) {
-            const int h = blockIdx.x + blockIdx.y * gridDim.x;
-            const int lid = (h & 7) * (total >> 3) + (h >> 3);
-            bx = lid % gridDim.x;
-            f = lid / gridDim.x;
+        const uint32_t gx = gridDim.x, total = gx * gridDim.y;
+        if ((total & 7) == 0 && gx_rcp != 0) {
+            const uint32_t h = blockIdx.x + blockIdx.y * gx;
+            const uint32_t lid = (h & 7) * (total >> 3) + (h >> 3);
+            f = (int)__umulhi(lid, gx_rcp);
+            bx = (int)(lid - (uint32_t)f * gx);
         }
     }
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int g = lane >> 4, sub = lane & 15;
     const int kslot = wave * FIN_KPW + g;  // keypoint slot in the workgroup
     const int idx = bx * (NW * FIN_KPW) + kslot;
-    int lvl = -1, k = 0, acc = 0;
-    for (int i = 0; i < nlevels; i++) {
-        const int c = ocnt[f * nlevels + i];
-        if (lvl < 0 && idx < acc + c) {
-            lvl = i;
-            k = idx - acc;
+    // The keypoint's level and its index in the level from the levels'
+    // inclusive count prefixes P_i (scalar: ocnt is read at uniform addresses,
+    // the first eight counts by independent loads): the prefixes are
+    // non-decreasing, so lvl = #{i : P_i <= idx}, and k = idx - P_(lvl-1) is the
+    // smallest of idx and the differences idx - P_i taken mod 2^32 (those with
+    // P_i > idx wrap to huge values). Past the last level both are unused.
+    int lvl = 0, acc = 0;
+    uint32_t ku = (uint32_t)idx;
+    {
+        const int* const oc = ocnt + f * nlevels;
+        int c8[8];
+#pragma unroll
+        for (int i = 0; i < 8; i++) c8[i] = oc[i < nlevels ? i : nlevels - 1];
+#pragma unroll
+        for (int i = 0; i < 8; i++) {
+            acc += i < nlevels ? c8[i] : 0;
+            lvl += idx >= acc ? 1 : 0;
+            ku = min(ku, (uint32_t)idx - (uint32_t)acc);
         }
-        acc += c;
+        for (int i = 8; i < nlevels; i++) {
+            acc += oc[i];
+            lvl += idx >= acc ? 1 : 0;
+            ku = min(ku, (uint32_t)idx - (uint32_t)acc);
+        }
     }
+    const int k = (int)ku;
     const int total = acc < kp_cap ? acc : kp_cap;
     if (bx == 0 && threadIdx.x == 0) nkp[f] = total;
     if (bx * (NW * FIN_KPW) >= total) return;  // uniform over the workgroup
-    const bool valid = lvl >= 0 && idx < kp_cap;
-    const LevelDesc L = lv[valid ? lvl : 0];
+    const bool valid = idx < acc && idx < kp_cap;
+    if (!valid) lvl = 0;
+    const LevelDesc L = lv[lvl];
     // an invalid slot stages and reads a dummy in-level patch and writes nothing
     const uint32_t key = valid ? okp[((size_t)f * nlevels + lvl) * okp_stride + k] : (16u | (16u << 12));
     const int kx = (int)(key & 0xfff) + 16, ky = (int)((key >> 12) & 0xfff) + 16;
@@ -263,10 +293,20 @@ __global__ void __launch_bounds__(64 * NW) k_finalize_lds(const uint8_t* __restr
         tv0[w] = PB[o0];
         tv1[w] = PB[o1];
     }
+    // all sixteen ballots first (scalar registers), then lane 0 stores them in
+    // one block: a store after each ballot was sixteen exec-mask branch
+    // blocks that every wave entered. The empty asm keeps the stores 64 bits
+    // wide, one v_mov_b64 each: merged into 128-bit stores they take two
+    // 32-bit moves per ballot
+    uint64_t bal[16];
 #pragma unroll
-    for (int w = 0; w < 16; w++) {
-        const uint64_t bal = __ballot(tv0[w] < tv1[w]);
-        if (lane == 0) s_bal[wave][w] = bal;
+    for (int w = 0; w < 16; w++) bal[w] = __ballot(tv0[w] < tv1[w]);
+    if (lane == 0) {
+#pragma unroll
+        for (int w = 0; w < 16; w++) {
+            s_bal[wave][w] = bal[w];
+            asm volatile("" ::: "memory");
+        }
     }
     __syncthreads();
     const int o = idx;
@@ -306,11 +346,6 @@ __global__ void __launch_bounds__(256) k_kp_geometry(const orb_kp* __restrict__ 
 }
 
 void upload_finalize_constants() {
-    float4 pat[256];
-    for (int t = 0; t < 256; t++)
-        pat[t] = make_float4((float)ODO_ORB_PATTERN[4 * t], (float)ODO_ORB_PATTERN[4 * t + 1],
-                             (float)ODO_ORB_PATTERN[4 * t + 2], (float)ODO_ORB_PATTERN[4 * t + 3]);
-    hipMemcpyToSymbol(HIP_SYMBOL(c_patf), pat, sizeof(pat));
     uint32_t pat8[256];
     for (int sl = 0; sl < 16; sl++)
         for (int w = 0; w < 16; w++) {
@@ -320,8 +355,6 @@ void upload_finalize_constants() {
             pat8[sl * 16 + w] = v;
         }
     hipMemcpyToSymbol(HIP_SYMBOL(c_pat8), pat8, sizeof(pat8));
-    const int umax[16] = {15, 15, 15, 15, 14, 14, 14, 13, 13, 12, 11, 10, 9, 8, 6, 3};
-    hipMemcpyToSymbol(HIP_SYMBOL(c_umax16), umax, sizeof(umax));
 }
 
 void launch_kp_geometry(hipStream_t st, const orb_kp* kps, const int* nkp, const uint16_t* depth, size_t depth_stride,
@@ -337,8 +370,12 @@ void launch_finalize(hipStream_t st, const uint8_t* pyr, const uint8_t* blur, si
                      float* ur, int* nkp, int kp_cap, int nframes, bool geometry) {
     // 2 waves (8 keypoints, 21 KB of LDS) per workgroup: more workgroups
     // resident per CU than at 4 waves (42.5 KB)
-    hipLaunchKernelGGL(k_finalize_lds<2>, dim3((kp_cap + 7) / 8, nframes), dim3(128), 0, st, pyr, blur, pyr_stride, lv,
-                       nlevels, okp, ocnt, okp_stride, kps, desc, nkp, kp_cap);
+    const uint32_t gx = (uint32_t)(kp_cap + 7) / 8;
+    const uint64_t ntot = (uint64_t)gx * (uint64_t)nframes;
+    // the kernel's XCD remap divides by gx with this reciprocal (0: no remap)
+    const uint32_t gx_rcp = gx > 1 && ntot * gx < (1ull << 32) ? (uint32_t)(((1ull << 32) + gx - 1) / gx) : 0u;
+    hipLaunchKernelGGL(k_finalize_lds<2>, dim3(gx, nframes), dim3(128), 0, st, pyr, blur, pyr_stride, lv, nlevels, okp,
+                       ocnt, okp_stride, kps, desc, nkp, kp_cap, gx_rcp);
     if (geometry) launch_kp_geometry(st, kps, nkp, depth, depth_stride, img_w, cal, kun, xyz, ur, kp_cap, nframes);
 }
 

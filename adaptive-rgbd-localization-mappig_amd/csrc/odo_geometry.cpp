@@ -287,6 +287,7 @@ int odo::build_geometry(odo_ctx* c) {
                         G.bw = (int16_t)((G.cols + 31) >> 5);
                         if ((A.x0 & 15) + G.cols > FS_RS || G.ncell > FS_NCM || G.rows > 70 || (int)G.rows * FS_RS > 65536)
                             return fail(ODO_ERR_ARG, "FAST segment too large");
+                        fast_seg_staging(G);
                         c->fsegs_h.push_back(G);
                     }
             } else if (nct > 0) {

@@ -69,8 +69,24 @@ struct CellDesc {
 struct FastSeg {
     int level, ci0;
     int16_t y0, x0, rows, cols, ncell, wcell;
-    int16_t bw, pad;  // kept-bitmap words per row
+    int16_t bw;  // kept-bitmap words per row
+    // per-segment constants the kernel would otherwise divide for
+    // (fast_seg_staging). The staging loop's thread grid: nw 16-byte columns
+    // per staged row, rstep = FS_TH / nw rows per step, and rmag =
+    // ceil(4096 / nw), with which t / nw = (t * rmag) >> 12 for every
+    // t < FS_TH (nw <= 17: the error term t * 16 stays below 4096)
+    int16_t nw, rstep, rmag;
+    float inv_w;  // 1.0f / (float)wcell
 };
+// 32 bytes: the kernel reads its segment as two 16-byte scalar loads
+static_assert(sizeof(FastSeg) == 32, "FastSeg is read as two uint4");
+inline void fast_seg_staging(FastSeg& G) {
+    const int nw = ((G.x0 & 15) + G.cols + 15) >> 4;
+    G.nw = (int16_t)nw;
+    G.rstep = (int16_t)(256 / nw);
+    G.rmag = (int16_t)((4096 + nw - 1) / nw);
+    G.inv_w = 1.0f / (float)G.wcell;
+}
 // k_fast_seg's dynamic LDS: byte offsets of its regions
 struct FastLds {
     int img;  // bytes of the staged ROI union (the score map follows at img)

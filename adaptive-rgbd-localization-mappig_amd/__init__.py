@@ -570,6 +570,35 @@ class Odometry:
         check(self.lib.odo_debug_select(self.h, ptr(keys), keys.size, nth, mode, ptr(out), C.byref(n)))
         return out, n.value
 
+    def match_features_buffers(self, n: int, fill: int = 0x5A):
+        """The output arrays of odo_debug_match_features for n frames, every
+        byte `fill`, and the odo_pair_stage_out that points at them."""
+        kc, m = self.kp_capacity(), n - 1
+        out = dict(lm_flags=np.empty((m, kc), np.uint8), qlist=np.empty((m, kc), np.int32),
+                   qcnt=np.empty(m, np.int32), knn_idx=np.empty((m, kc, 2), np.int32),
+                   knn_dist=np.empty((m, kc, 2), np.int32), matches=np.empty((m, kc), DMATCH_DTYPE),
+                   n_matches=np.empty(m, np.int32), good=np.empty((m, kc), DMATCH_DTYPE),
+                   n_good=np.empty(m, np.int32), f2_src=np.empty((m, kc), np.int32), latch=np.empty(1, np.float64))
+        for a in out.values():
+            a.view(np.uint8).fill(fill)
+        return out, _abi.PairStageOut(**{k: a.ctypes.data for k, a in out.items()})
+
+    def match_features(self, frames, fill: int = 0x5A):
+        """odo_debug_match_features: the pair-match stage (VO landmarks, kNN-2,
+        k_pair_match, latch) on len(frames) frames of (desc [cnt, 32] u8,
+        xyz [cnt, 3] f32); pair p is (frame p, frame p + 1). Returns the full
+        output arrays: what the call did not write still holds `fill` bytes."""
+        kc, n = self.kp_capacity(), len(frames)
+        counts = np.array([len(d) for d, _ in frames], np.int32)
+        desc = np.full((n, kc, 32), fill, np.uint8)
+        xyz = np.full((n, kc, 3), np.nan, np.float32)
+        for i, (d, x) in enumerate(frames):
+            desc[i, :len(d)] = d
+            xyz[i, :len(d)] = x
+        out, st = self.match_features_buffers(n, fill)
+        check(self.lib.odo_debug_match_features(self.h, n, ptr(counts), ptr(desc), ptr(xyz), C.byref(st)))
+        return out
+
     def pnp_ransac(self, Xw, uv, calib=None, iterations: int = 500, reproj_err: float = 3.0,
                    confidence: float = 0.85):
         """PnPRansac::Compute (pnpransac.cpp:11-51) on the GPU: cv::solvePnPRansac

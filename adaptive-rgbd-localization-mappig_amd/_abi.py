@@ -105,6 +105,12 @@ class CloudInfo(C.Structure):
                 ("div_b", C.c_int32 * 3), ("min_p", C.c_float * 3), ("max_p", C.c_float * 3)]
 
 
+class PairStageOut(C.Structure):
+    """odo_pair_stage_out (include/odo.h): host output pointers of odo_debug_match_features."""
+    _fields_ = [(n, P) for n in ("lm_flags", "qlist", "qcnt", "knn_idx", "knn_dist", "matches", "n_matches",
+                                 "good", "n_good", "f2_src", "latch")]
+
+
 BA_RAN, BA_NOTHING = 0, 1  # include/odo_types.h ODO_BA_*
 CLOUD_OK, CLOUD_UNFILTERED = 0, 1  # include/odo_types.h ODO_CLOUD_*
 ODOMETRY_ADAPTIVE_RBA = 0   # include/odo.h ODO_ODOMETRY_ADAPTIVE_RBA
@@ -212,6 +218,7 @@ SIGNATURES = {
     "odo_debug_fast": (C.c_int, [P, C.c_int, C.c_int, P, C.c_int, P]),
     "odo_debug_octree": (C.c_int, [P, C.c_int, C.c_int, P, C.c_int, P]),
     "odo_debug_sort": (C.c_int, [P, P, C.c_int, P]),
+    "odo_debug_match_features": (C.c_int, [P, C.c_int, P, P, P, P]),
     "odo_knn_replay_time": (C.c_int, [P, C.c_int, C.POINTER(C.c_float)]),
     "odo_set_timing": (C.c_int, [P, C.c_int]),
     "odo_kernel_timing": (C.c_int, [P, P, P]),

@@ -1136,6 +1136,10 @@ __global__ void k_latch(double* __restrict__ latch, const SortEl* __restrict__ g
         for (int k = 0; k < ng; k++) {
             const odo_dmatch m = M[G[k].val];
             if (X1[3 * m.queryIdx + 2] == 0.0f || X2[3 * m.trainIdx] == 0.0f) continue;
+            // ErrorFunction2 returns on a NaN depth of either point before it
+            // calls DepthCovariance (ransac.cpp:362-365): such a match (kept by
+            // the filter only with check_depth off) does not latch
+            if (__builtin_isnan(X1[3 * m.queryIdx + 2]) || __builtin_isnan(X2[3 * m.trainIdx + 2])) continue;
             const double z = (double)X1[3 * m.queryIdx + 2];
             const double sd = 0.01 * z * z;
             *latch = sd * sd;

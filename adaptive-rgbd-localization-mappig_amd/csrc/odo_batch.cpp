@@ -205,17 +205,15 @@ static void run_ricp(odo_ctx* c, hipStream_t st, int set, int n) {
                       n);
 }
 
-// Pair stages of one batch on its pair stream `st`, over frame set `set`:
-// pair p is (slot p, slot p+1); pair 0 is valid only with a previous frame.
-// `latched`: the DepthCovariance latch is known to hold its value (track_batch),
-// so the latch kernel is left out. `defer_done`: the caller records the set's
-// PnP-done event itself, after the result copy it queues behind the PnP.
-static int run_pairs(odo_ctx* c, hipStream_t st, int set, int n, bool latched, bool defer_done) {
+// The match stage of the n pairs of frame set `set` on stream `st`: the pair
+// flags (pair 0 valid only with `first_valid`), k_pair_match and, unless
+// `latched`, the DepthCovariance latch. Shared by run_pairs and
+// odo_debug_match_features, so the two cannot drift apart.
+int odo::run_pair_match(odo_ctx* c, hipStream_t st, int set, int n, bool first_valid, bool latched) {
     auto& P = c->pb[set];
     const size_t KC = (size_t)c->kp_cap;
     const FrameSlot f = frame_at(c, fbase(c, set));
-    tmark(c, 6, st);
-    launch_pair_valid(st, P.pair_valid, n, c->has_prev ? 1 : 0);
+    launch_pair_valid(st, P.pair_valid, n, first_valid ? 1 : 0);
     launch_pair_match(st, c->knn_idx[set], c->knn_dist[set], KC, f.xyz, f.nkp, c->kp_cap, 0, c->cfg.nn_ratio,
                       c->lm_bits[set], c->lm_words, c->knn_split, (size_t)c->maxb * KC, c->cfg.ransac.check_depth,
                       P.matches, P.n_matches, P.good, P.n_good, P.f2_src, c->sort_scratch, c->match_cap, n);
@@ -232,6 +230,20 @@ static int run_pairs(odo_ctx* c, hipStream_t st, int set, int n, bool latched, b
         HIPCHK(hipEventRecord(c->ev_latch, st));
         c->latch_rec = true;
     }
+    return ODO_OK;
+}
+
+// Pair stages of one batch on its pair stream `st`, over frame set `set`:
+// pair p is (slot p, slot p+1); pair 0 is valid only with a previous frame.
+// `latched`: the DepthCovariance latch is known to hold its value (track_batch),
+// so the latch kernel is left out. `defer_done`: the caller records the set's
+// PnP-done event itself, after the result copy it queues behind the PnP.
+static int run_pairs(odo_ctx* c, hipStream_t st, int set, int n, bool latched, bool defer_done) {
+    auto& P = c->pb[set];
+    const FrameSlot f = frame_at(c, fbase(c, set));
+    int e;
+    tmark(c, 6, st);
+    if ((e = run_pair_match(c, st, set, n, c->has_prev, latched))) return e;
     tmark(c, 7, st);
     // RANSAC, then one PnP launch for the whole batch, back to back on the
     // batch's own pair stream: nothing else waits for RANSAC alone, so no
@@ -308,7 +320,7 @@ void odo::launch_set_knn2(odo_ctx* c, hipStream_t st, int s, int n) {
 }
 
 // kNN-2 of the batch's pairs on stream `st` (an event pair around it in timing mode 2)
-static int run_knn(odo_ctx* c, hipStream_t st, int s, int n) {
+int odo::run_knn(odo_ctx* c, hipStream_t st, int s, int n) {
     const FrameSlot f = frame_at(c, fbase(c, s));
     // the query frames' VO landmarks first: kNN-2 runs on their keypoints only
     const float mThDepth = c->cfg.calib.mbf * c->cfg.calib.th_depth / c->cfg.calib.fx;

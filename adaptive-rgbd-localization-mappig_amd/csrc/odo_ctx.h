@@ -443,6 +443,8 @@ int reset_adaptive(odo_ctx* c);
 int run_extract(odo_ctx* c, int set, const uint8_t* d_bgr, const uint16_t* d_depth, int n, int slot0,
                 bool geometry = true);         // odo_batch.cpp
 void launch_set_knn2(odo_ctx* c, hipStream_t st, int s, int n);
+int run_knn(odo_ctx* c, hipStream_t st, int s, int n);  // k_vo_lm + launch_set_knn2
+int run_pair_match(odo_ctx* c, hipStream_t st, int set, int n, bool first_valid, bool latched);
 void free_local_map(odo_ctx* c);               // odo_stages.cpp
 void free_dense_clouds(odo_ctx* c);            // odo_cloud.cpp
 void free_hyp_session(HypSession* h);          // odo_hyps.cpp

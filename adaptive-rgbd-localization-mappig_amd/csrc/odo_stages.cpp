@@ -109,6 +109,102 @@ int odo_knn2_hamming(odo_ctx* c, const uint8_t* q, int nq, const uint8_t* t, int
     return ODO_OK;
 }
 
+// The pair-match stage on caller-supplied features (tests). Frame i goes to
+// slot i of the set the next batch would use: frame 0 where the roll puts the
+// previous frame, the others where extraction puts a batch's frames. The
+// launches are the batch path's own (run_knn, run_pair_match).
+int odo_debug_match_features(odo_ctx* c, int n, const int32_t* counts, const uint8_t* desc, const float* xyz,
+                             const odo_pair_stage_out* out) {
+    if (!c || !counts || !desc || !xyz || !out) return fail(ODO_ERR_ARG, "match_features: null argument");
+    if (n < 2 || n > c->maxb + 1) return fail(ODO_ERR_ARG, "match_features: 2 .. max_batch + 1 frames");
+    if (!out->lm_flags || !out->qlist || !out->qcnt || !out->knn_idx || !out->knn_dist || !out->matches ||
+        !out->n_matches || !out->good || !out->n_good || !out->f2_src || !out->latch)
+        return fail(ODO_ERR_ARG, "match_features: null output");
+    for (int i = 0; i < n; i++)
+        if (counts[i] < 0) return fail(ODO_ERR_ARG, "match_features: negative count");
+    for (int i = 0; i < n; i++)
+        if (counts[i] > c->kp_cap) return fail(ODO_ERR_CAPACITY, "match_features: count above odo_kp_capacity");
+    int e;
+    if ((e = sync_all(c))) return e;
+    const int set = next_set(c), np = n - 1, nsplit = c->knn_split;
+    const size_t KC = (size_t)c->kp_cap, SS = (size_t)c->maxb * KC;
+    const FrameSlot f = frame_at(c, fbase(c, set));
+    hipStream_t st = c->stream;
+    HIPCHK(hipMemcpy(f.nkp, counts, (size_t)n * sizeof(int), hipMemcpyHostToDevice));
+    for (int i = 0; i < n; i++) {
+        if (counts[i] == 0) continue;
+        HIPCHK(hipMemcpy(f.desc + i * KC * 32, desc + i * KC * 32, (size_t)counts[i] * 32, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(f.xyz + i * KC * 3, xyz + i * KC * 3, (size_t)counts[i] * 12, hipMemcpyHostToDevice));
+    }
+    if ((e = run_knn(c, st, set, np))) return e;
+    if ((e = run_pair_match(c, st, set, np, true, false))) return e;
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(st));
+    auto& P = c->pb[set];
+    std::vector<uint32_t> bits((size_t)np * c->lm_words);
+    std::vector<int32_t> ql((size_t)np * KC), src((size_t)np * KC);
+    std::vector<int> qc(np), nm(np), ng(np);
+    std::vector<int2> ki((size_t)nsplit * SS), kd((size_t)nsplit * SS);
+    std::vector<odo_dmatch> M((size_t)np * KC);
+    std::vector<uint64_t> G((size_t)np * KC);
+    HIPCHK(hipMemcpy(bits.data(), c->lm_bits[set], bits.size() * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(ql.data(), c->qlist[set], ql.size() * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(qc.data(), c->qcnt[set], (size_t)np * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(ki.data(), c->knn_idx[set], ki.size() * sizeof(int2), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(kd.data(), c->knn_dist[set], kd.size() * sizeof(int2), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(M.data(), P.matches, M.size() * sizeof(odo_dmatch), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(G.data(), P.good, G.size() * 8, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(nm.data(), P.n_matches, (size_t)np * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(ng.data(), P.n_good, (size_t)np * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(src.data(), P.f2_src, src.size() * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(out->latch, c->latch, sizeof(double), hipMemcpyDeviceToHost));
+    // the context as after odo_reset, whatever the counts below turn out to be
+    c->view_mode = -1;
+    c->last_n = 0;
+    c->lm_n = -1;
+    if ((e = odo_reset(c))) return e;
+    for (int p = 0; p < np; p++) {
+        const int n1 = counts[p], n2 = counts[p + 1];
+        const size_t o = (size_t)p * KC;
+        if (qc[p] < 0 || qc[p] > n1 || nm[p] < 0 || nm[p] > c->match_cap || ng[p] < 0 || ng[p] > nm[p])
+            return fail(ODO_ERR_STATE, "match_features: a count the kernels wrote is out of range");
+        out->qcnt[p] = qc[p];
+        out->n_matches[p] = nm[p];
+        out->n_good[p] = ng[p];
+        memcpy(out->qlist + o, ql.data() + o, (size_t)qc[p] * 4);
+        memcpy(out->matches + o, M.data() + o, (size_t)nm[p] * sizeof(odo_dmatch));
+        memcpy(out->f2_src + o, src.data() + o, (size_t)n2 * 4);
+        for (int i = 0; i < n1; i++) {
+            const bool lm = (bits[(size_t)p * c->lm_words + (i >> 5)] >> (i & 31)) & 1u;
+            out->lm_flags[o + i] = lm ? 1 : 0;
+            if (!lm) continue;  // kNN-2 ran on the landmark queries only
+            // the splits' top-2 lists as one: the two smallest (distance, index)
+            std::pair<int, int> best[2] = {{0x7FFFFFFF, -1}, {0x7FFFFFFF, -1}};
+            for (int h = 0; h < nsplit; h++) {
+                const int2 I = ki[(size_t)h * SS + o + i], D = kd[(size_t)h * SS + o + i];
+                const std::pair<int, int> cand[2] = {{D.x, I.x}, {D.y, I.y}};
+                for (const auto& k : cand) {
+                    if (k.second < 0) continue;
+                    if (k < best[0]) {
+                        best[1] = best[0];
+                        best[0] = k;
+                    } else if (k < best[1]) best[1] = k;
+                }
+            }
+            for (int k = 0; k < 2; k++) {
+                out->knn_idx[2 * (o + i) + k] = best[k].second;
+                out->knn_dist[2 * (o + i) + k] = best[k].first;
+            }
+        }
+        for (int k = 0; k < ng[p]; k++) {
+            const uint32_t at = (uint32_t)(G[o + k] >> 32);  // SortEl.val: position in the match list
+            if (at >= (uint32_t)nm[p]) return fail(ODO_ERR_STATE, "match_features: good match outside the match list");
+            out->good[o + k] = M[o + at];
+        }
+    }
+    return ODO_OK;
+}
+
 int odo_pnp_motion_ba(odo_ctx* c, const float* Xw, const float* obs, int n, const odo_calib* calib,
                       const float Tcw_init[16], float Tcw_out[16], uint8_t* outlier, int* n_inliers) {
     if (!c || n < 0 || (n && (!Xw || !obs)) || !Tcw_init || !Tcw_out || !n_inliers) return fail(ODO_ERR_ARG, "bad pnp args");

@@ -643,6 +643,45 @@ int odo_debug_blur(odo_ctx* ctx, int i, uint8_t* out, size_t cap);
  * distance in libstdc++'s exact (unstable) order; distances must be >= 0. */
 int odo_debug_sort(odo_ctx* ctx, const odo_dmatch* in, int n, odo_dmatch* out);
 
+/* The pair-match stage on caller-supplied features: the batch path's own
+ * launches with its own arguments (VO landmarks and query list, kNN-2 in the
+ * context's form and split count, k_pair_match, the DepthCovariance latch) on
+ * n host frames, without extraction, RANSAC or the pose stage.
+ * counts[n]; desc [n][kp_cap][32] and xyz [n][kp_cap][3] with kp_cap =
+ * odo_kp_capacity(ctx), of which the first counts[i] rows of frame i are read.
+ * Frame i is placed in slot i of the frame set the next batch would use
+ * (frame 0 where the roll puts the previous frame, the others where
+ * extraction puts a batch's frames), so pair p is (frame p, frame p + 1):
+ * n - 1 pairs, every one valid; 2 <= n <= max_batch + 1. Configuration is the
+ * context's (nn_ratio, ransac.check_depth, ransac.min_inlier_th, calib for
+ * mThDepth, forms.knn, forms.knn_split); the latch is read as odo_set_latch
+ * left it, and *latch is its value after the batch. Every output array holds
+ * n - 1 rows of kp_cap entries (qcnt, n_matches, n_good: n - 1 entries); only
+ * the entries named are written:
+ *   lm_flags   counts[p] flags of frame p's VO landmarks
+ *   qlist      qcnt[p] landmark keypoint indices, ascending
+ *   knn_idx/knn_dist  [kp_cap][2], the rows of landmark queries only: the
+ *              train splits' lists merged (-1 / INT_MAX when absent)
+ *   matches    n_matches[p] KnnMatch results in query order
+ *   good       n_good[p] good matches in std::sort's order
+ *   f2_src     counts[p + 1] entries: the frame-p keypoint whose landmark
+ *              sits in this frame-(p + 1) slot, or -1
+ * A null pointer or a negative count is ODO_ERR_ARG and a count above kp_cap
+ * ODO_ERR_CAPACITY, both before anything else is read or written. The call
+ * synchronises and ends with odo_reset: a later odo_track_batch* behaves as
+ * it does after odo_reset (no previous frame, latch unset, pair counter 0). */
+typedef struct odo_pair_stage_out {
+    uint8_t* lm_flags;
+    int32_t *qlist, *qcnt, *knn_idx, *knn_dist;
+    odo_dmatch* matches;
+    int32_t* n_matches;
+    odo_dmatch* good;
+    int32_t *n_good, *f2_src;
+    double* latch;
+} odo_pair_stage_out;
+int odo_debug_match_features(odo_ctx* ctx, int n, const int32_t* counts, const uint8_t* desc, const float* xyz,
+                             const odo_pair_stage_out* out);
+
 /* Measurement only (no reference counterpart): re-runs the most recent
  * batch's kNN-2 launch `reps` times on an idle device and returns its mean
  * duration in ms (HIP events). The bench's roofline "alone" figure. */

@@ -77,6 +77,8 @@ def test_track_entry_points_reject_a_null_context():
                  "odo_track_batch_host_sparse_depth"):
         assert getattr(lib, name)(None, buf, buf, 1, buf) == -1, name
         assert lib.odo_last_error()
+    assert lib.odo_debug_match_features(None, 2, buf, buf, buf, buf) == -1
+    assert lib.odo_debug_match_features(None, 2, None, None, None, None) == -1
 
 
 @pytest.mark.skipif(gpu_available(), reason="checks the no-GPU failure path")

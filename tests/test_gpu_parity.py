@@ -262,13 +262,16 @@ def test_device_pipelined_batches_equal_host_path():
 def test_good_match_sort_is_std_sort(pkg, n, levels):
     """The pair stage's workgroup-parallel introsort returns exactly
     libstdc++'s std::sort permutation (ties included: Hamming distances take
-    few values), against the oracle's std::sort on the same DMatch array."""
+    few values), against the oracle's std::sort on the same DMatch array. None
+    of these inputs reaches the introsort's depth limit (presorted runs are the
+    median of three's best case): the heap branch runs in
+    test_pair_stage_gpu.py::test_sort_alone_at_the_depth_limit."""
     rng = np.random.default_rng(n * 31 + levels)
     m = np.zeros(n, O.DMATCH_DTYPE)
     m["queryIdx"] = np.arange(n)
     m["trainIdx"] = rng.integers(0, 5000, n)
     m["distance"] = rng.integers(0, levels, n).astype(np.float32)
-    if n > 100:  # presorted and reversed runs stress the median-of-3 / depth limit
+    if n > 100:  # presorted and reversed runs: long stretches without a swap, pivots equal to many keys
         k = n // 3
         m["distance"][:k] = np.sort(m["distance"][:k])
         m["distance"][k:2 * k] = np.sort(m["distance"][k:2 * k])[::-1]

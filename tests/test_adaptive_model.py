@@ -14,42 +14,17 @@ detectoradjuster.cpp, extractor.cpp:39-77):
 * the single-range parallel Hoare partition model of libstdc++'s introselect
   (what the GPU runs for keepStrongest / retainBest) returns exactly
   std::nth_element's permutation.
+
+The model itself lives in tests/adaptive_ref.py, which also carries the
+heap-select fallback these inputs do not reach (tests/test_adaptive_ref.py
+reaches it with adversarial inputs).
 """
 import numpy as np
 import pytest
 
 import oracle_lib as O
+from adaptive_ref import cell_geometry, chain_step, introselect_model, model_fast, s_map
 from conftest import sequence
-
-CIRCLE = [(0, 3), (1, 3), (2, 2), (3, 1), (3, 0), (3, -1), (2, -2), (1, -3),
-          (0, -3), (-1, -3), (-2, -2), (-3, -1), (-3, 0), (-3, 1), (-2, 2), (-1, 3)]
-
-
-def s_map(img):
-    """S(p) for p in [3,h-3)x[3,w-3), 0 elsewhere (int32)."""
-    h, w = img.shape
-    v = img[3:h - 3, 3:w - 3].astype(np.int32)
-    d = np.stack([v - img[3 + dy:h - 3 + dy, 3 + dx:w - 3 + dx].astype(np.int32) for dx, dy in CIRCLE])
-    best = np.zeros_like(v)
-    for k in range(16):
-        arc = d[[(k + i) % 16 for i in range(9)]]
-        best = np.maximum(best, np.maximum(arc.min(0), (-arc).min(0)))
-    S = np.zeros((h, w), np.int32)
-    S[3:h - 3, 3:w - 3] = best
-    return S
-
-
-def model_fast(S_roi, t):
-    """Keypoints of cv::FAST(roi, t, nonmax) from the ROI's S map (row-major)."""
-    rows, cols = S_roi.shape
-    R = np.zeros_like(S_roi)
-    R[3:rows - 3, 3:cols - 3] = S_roi[3:rows - 3, 3:cols - 3]  # detection region only
-    P = np.pad(R, 1)
-    nb = np.stack([P[1 + dy:1 + dy + rows, 1 + dx:1 + dx + cols] for dy in (-1, 0, 1) for dx in (-1, 0, 1)
-                   if dy or dx]).max(0)
-    keep = (R > t) & (R >= 2) & (R > nb)  # score S-1 >= 1: a 0 score never passes the NMS
-    ys, xs = np.nonzero(keep)
-    return xs, ys, R[ys, xs] - 1
 
 
 def oracle_fast(img, y0, x0, rows, cols, t):
@@ -77,35 +52,6 @@ def test_fast_is_thresholded_s_map(t):
         assert np.array_equal(ref["response"], resp.astype(np.float32))
 
 
-def cell_geometry(w, h, p):
-    cells = []
-    for i in range(p.grid_rows):
-        rs, re = max(i * h // p.grid_rows - p.edge_threshold, 0), min(h, (i + 1) * h // p.grid_rows + p.edge_threshold)
-        for j in range(p.grid_cols):
-            cs, ce = max(j * w // p.grid_cols - p.edge_threshold, 0), min(w, (j + 1) * w // p.grid_cols + p.edge_threshold)
-            cells.append((rs, re, cs, ce))
-    return cells
-
-
-def chain_step(thresh, count_above, p):
-    """VideoDynamicAdaptedFeatureDetector::detect replayed on count_above[t]."""
-    it = p.escape_iters
-    while True:
-        t = min(max(int(thresh), 0), 255)
-        n = int(count_above[t])
-        if n < p.cell_min:
-            thresh = max(thresh * p.decrease_factor, p.min_thresh)
-        elif n > p.cell_max:
-            thresh = min(thresh * p.increase_factor, p.max_thresh)
-            break
-        else:
-            break
-        it -= 1
-        if not (it > 0 and p.min_thresh < thresh < p.max_thresh):
-            break
-    return thresh, t
-
-
 def test_threshold_chain_matches_oracle():
     bgr, _, _ = sequence(6)
     ex = O.AdaptiveExtractor()
@@ -125,53 +71,6 @@ def test_threshold_chain_matches_oracle():
             thresh[c], t_used = chain_step(thresh[c], above, p)
             assert t_used == t_ref[c], (f, c)
         assert np.array_equal(thresh, ex.thresh), f"frame {f}"
-
-
-# ---- introselect model (single range per level, parallel Hoare partition)
-def introselect_model(a, nth, key):
-    a = list(a)
-    n = len(a)
-    if n == 0 or nth == n:
-        return a
-    first, last = 0, n
-    depth = 2 * (n.bit_length() - 1)
-    while last - first > 3:
-        if depth == 0:
-            raise NotImplementedError("heap_select")  # not reached by these inputs
-        depth -= 1
-        mid = first + (last - first) // 2
-        x, y, z = first + 1, mid, last - 1
-        kx, ky, kz = key(a[x]), key(a[y]), key(a[z])
-        if kx < ky:
-            m = y if ky < kz else (z if kx < kz else x)
-        else:
-            m = x if kx < kz else (z if ky < kz else y)
-        a[first], a[m] = a[m], a[first]
-        pk = key(a[first])
-        L = [j for j in range(first + 1, last) if key(a[j]) >= pk]
-        R = [j for j in range(last - 1, first, -1) if key(a[j]) <= pk]
-        ks = sum(1 for k in range(min(len(L), len(R))) if L[k] < R[k])
-        for k in range(ks):
-            a[L[k]], a[R[k]] = a[R[k]], a[L[k]]
-        cut = L[ks] if ks < len(L) else last
-        if ks > 0:
-            cut = min(cut, R[ks - 1])
-        if cut <= nth:
-            first = cut
-        else:
-            last = cut
-    for i in range(first + 1, last):  # __insertion_sort
-        v = a[i]
-        if key(v) < key(a[first]):
-            a[first + 1:i + 1] = a[first:i]
-            a[first] = v
-        else:
-            j = i
-            while key(v) < key(a[j - 1]):
-                a[j] = a[j - 1]
-                j -= 1
-            a[j] = v
-    return a
 
 
 @pytest.mark.parametrize("seed", range(12))

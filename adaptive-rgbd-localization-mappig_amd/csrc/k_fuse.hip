@@ -11,10 +11,11 @@
 // (odo_fuse_best, DESIGN.md §4 Fuse).
 //
 //   k_fuse_bin     one workgroup per call: the keyframe's keypoints
-//                  counting-sorted into the uniform grid (k_lm_bin's scheme),
+//                  counting-sorted into the uniform grid (lmk_bin, odo_kpgrid.h),
 //                  each sorted point with its right coordinate and its index
-//   k_fuse_search  one thread per (call, list entry): the projection, then the
-//                  grid cells under the window; the sorted points pass through
+//   k_fuse_search  one thread per (call, list entry): the projection
+//                  (lmk_camera, lmk_pixel_fuse, odo_kpgrid.h), then the grid
+//                  cells under the window; the sorted points pass through
 //                  LDS FZ_CHUNK at a time, a descriptor is read only for a
 //                  gated keypoint. Grid order is not keypoint order: the best
 //                  is the minimum of the key distance << 13 | index, the
@@ -31,47 +32,12 @@ __global__ void __launch_bounds__(256) k_fuse_bin(const odo_fuse_kf* __restrict_
                                                   const float* __restrict__ ur, const int32_t* __restrict__ kp_off,
                                                   LmGrid G, float4* __restrict__ bpt, int* __restrict__ cstart) {
     extern __shared__ __attribute__((aligned(16))) int s_cnt[];  // ncells + 1
-    const int c = blockIdx.x, ncells = G.gx * G.gy;
+    const int c = blockIdx.x;
     const int k0 = kfs[c].kp_begin, n = kfs[c].kp_end - k0;
-    const float* K = kun + (size_t)k0 * 2;
     const float* R = ur + k0;
     float4* out = bpt + kp_off[c];
-    for (int q = threadIdx.x; q <= ncells; q += blockDim.x) s_cnt[q] = 0;
-    __syncthreads();
-    for (int j = threadIdx.x; j < n; j += blockDim.x) {
-        const int cell = lmk_cell(K[2 * j + 1] - G.y0, G.inv, G.gy) * G.gx + lmk_cell(K[2 * j] - G.x0, G.inv, G.gx);
-        atomicAdd(&s_cnt[cell], 1);
-    }
-    __syncthreads();
-    // exclusive scan by wave 0: a run of cells per lane, then the lanes' totals
-    if (threadIdx.x < 64) {
-        const int per = (ncells + 63) / 64, c0 = min((int)threadIdx.x * per, ncells), c1 = min(c0 + per, ncells);
-        int sum = 0;
-        for (int q = c0; q < c1; q++) sum += s_cnt[q];
-        int inc = sum;
-        for (int o = 1; o < 64; o <<= 1) {
-            const int t = __shfl_up(inc, o);
-            if ((int)threadIdx.x >= o) inc += t;
-        }
-        int run = inc - sum;
-        for (int q = c0; q < c1; q++) {
-            const int t = s_cnt[q];
-            s_cnt[q] = run;
-            run += t;
-        }
-        if (threadIdx.x == 63) s_cnt[ncells] = inc;
-    }
-    __syncthreads();
-    int* cs = cstart + (size_t)c * (ncells + 1);
-    for (int q = threadIdx.x; q <= ncells; q += blockDim.x) cs[q] = s_cnt[q];
-    __syncthreads();
-    // the order inside a cell is whatever the atomics give: the search keys on the index
-    for (int j = threadIdx.x; j < n; j += blockDim.x) {
-        const float x = K[2 * j], y = K[2 * j + 1];
-        const int cell = lmk_cell(y - G.y0, G.inv, G.gy) * G.gx + lmk_cell(x - G.x0, G.inv, G.gx);
-        const int pos = atomicAdd(&s_cnt[cell], 1);
-        out[pos] = make_float4(x, y, R[j], __int_as_float(j));
-    }
+    lmk_bin(kun + (size_t)k0 * 2, n, G, s_cnt, cstart + (size_t)c * (G.gx * G.gy + 1),
+            [&](int pos, int j, float x, float y) { out[pos] = make_float4(x, y, R[j], __int_as_float(j)); });
 }
 
 __global__ void __launch_bounds__(256) k_fuse_search(const odo_fuse_kf* __restrict__ kfs,
@@ -105,23 +71,17 @@ __global__ void __launch_bounds__(256) k_fuse_search(const odo_fuse_kf* __restri
             const float* T = kfs[c].Tcw;
             nc = ODO_FUSE_BAD;
             if (!(L.flags & ODO_LM_BAD)) {
-                // the folded gemm of k_proj_cands; then matcher.cpp:231-244
-                float Pc[3];
-#pragma unroll
-                for (int k = 0; k < 3; k++)
-                    Pc[k] = (float)((((double)T[4 * k] * L.X[0] + (double)T[4 * k + 1] * L.X[1]) +
-                                     (double)T[4 * k + 2] * L.X[2]) + (double)T[4 * k + 3]);
+                // matcher.cpp:231-244: a NaN pixel fails these bounds, the upper ones are exclusive
+                const LmkCam Pc = lmk_camera(T, L.X);
                 nc = ODO_FUSE_BEHIND;
-                if (!(Pc[2] < 0.0f)) {
-                    const float invz = 1.0f / Pc[2];
-                    const float x = Pc[0] * invz, y = Pc[1] * invz;
-                    const float uu = C.fx * x + C.cx, vv = C.fy * y + C.cy;
+                if (!(Pc.z < 0.0f)) {
+                    const LmkPix p = lmk_pixel_fuse(Pc, C);
                     nc = ODO_FUSE_OUTSIDE;
-                    if (uu >= C.minX && uu < C.maxX && vv >= C.minY && vv < C.maxY) {
+                    if (p.u >= C.minX && p.u < C.maxX && p.v >= C.minY && p.v < C.maxY) {
                         nc = 0;
-                        u = uu;
-                        v = vv;
-                        ur = uu - C.mbf * invz;
+                        u = p.u;
+                        v = p.v;
+                        ur = p.ur;
                     }
                 }
             }
@@ -141,32 +101,28 @@ __global__ void __launch_bounds__(256) k_fuse_search(const odo_fuse_kf* __restri
         __syncthreads();  // the chunk before is read out (and s_cs is written, the first time round)
         for (int k = c0 + threadIdx.x; k < c1; k += blockDim.x) s_pt[k - c0] = P[k];
         __syncthreads();
-        for (int cy = r.cy0; cy <= r.cy1; cy++) {
-            const int ke = min(s_cs[cy * G.gx + r.cx1 + 1], c1);
-            for (int k = max(s_cs[cy * G.gx + r.cx0], c0); k < ke; k++) {
-                const float4 q = s_pt[k - c0];
-                const float dx = q.x - u, dy = q.y - v;
-                if (!(fabsf(dx) < th && fabsf(dy) < th)) continue;
-                const float ex = u - q.x, ey = v - q.y;
-                float e2 = ex * ex + ey * ey, lim = 5.99f;
-                if (q.z >= 0.0f) {
-                    const float er = ur - q.z;
-                    e2 = e2 + er * er;
-                    lim = 7.8f;
-                }
-                if (e2 > lim) continue;
-                uint32_t j = (uint32_t)__float_as_int(q.w);
-                best = min(best, ((uint32_t)lmk_hamming(ld, D + 32 * (size_t)j) << 13) | j);
-                nc++;
-                // sorted insert: cd stays the 8 smallest indices, ascending
-#pragma unroll
-                for (int k2 = 0; k2 < ODO_FUSE_CANDS; k2++) {
-                    const uint32_t lo = min(cd[k2], j);
-                    j = max(cd[k2], j);
-                    cd[k2] = lo;
-                }
+        lmk_for_window(r, s_cs, G, c0, c1, 0, 1, [&](int k) {
+            const float4 q = s_pt[k - c0];
+            if (!lmk_in_window(q.x, q.y, u, v, th)) return;
+            const float ex = u - q.x, ey = v - q.y;
+            float e2 = ex * ex + ey * ey, lim = 5.99f;
+            if (q.z >= 0.0f) {
+                const float er = ur - q.z;
+                e2 = e2 + er * er;
+                lim = 7.8f;
             }
-        }
+            if (e2 > lim) return;
+            uint32_t j = (uint32_t)__float_as_int(q.w);
+            best = min(best, ((uint32_t)lmk_hamming(ld, D + 32 * (size_t)j) << 13) | j);
+            nc++;
+            // sorted insert: cd stays the 8 smallest indices, ascending
+#pragma unroll
+            for (int k2 = 0; k2 < ODO_FUSE_CANDS; k2++) {
+                const uint32_t lo = min(cd[k2], j);
+                j = max(cd[k2], j);
+                cd[k2] = lo;
+            }
+        });
     }
     if (!active) return;
     odo_fuse_cand o;

@@ -3,21 +3,23 @@
 // then Matcher(0.8f)::ProjectionMatch, matcher.cpp:90-145, over
 // GetFeaturesInArea's window, frame.cpp:258-274) against one shared landmark
 // array, the merge with the slots KnnMatch carried over, and the edge gather
-// for the second PnPSolver::Compute (k_pnp, unchanged). The frames are read in
-// their batch slots. Semantics: k_project.hip (one frame, host inputs); this
-// file is the batched form, one launch chain for all frames.
+// for the second PnPSolver::Compute (k_pnp, unchanged). One launch chain for
+// all frames of a search: odo_track_local_map searches the frames of a batch
+// where they sit, odo_projection_match one frame of host inputs. The
+// projection, the grid and the window walk are odo_kpgrid.h's.
 //
 //   k_lm_prior    per frame: prior slots holding a BAD landmark are released
 //                 (UpdateLocalKFs, tracking.cpp:270-276), the rest mark their
 //                 landmark SEEN in the frame's bitmask (tracking.cpp:371-382)
 //                 and their slot taken iff the landmark has observations
-//                 (matcher.cpp:114-117)
+//                 (matcher.cpp:114-117); without a prior the taken slots are
+//                 the caller's, or none
 //   k_lm_bin      per frame: the undistorted keypoints counting-sorted into a
 //                 uniform grid (row-major cells, so the cells a window covers
 //                 in one cell row are one contiguous run of the sorted points)
-//   k_lm_cands    one thread per (frame, landmark): the projection with
-//                 k_proj_cands' arithmetic, then only the grid cells under the
-//                 window (the frame's sorted points staged in LDS); a
+//   k_lm_cands    one thread per (frame, landmark): the projection
+//                 (lmk_camera, lmk_pixel_frustum), then only the grid cells under
+//                 the window (the frame's sorted points staged in LDS); a
 //                 candidate is the key distance << 18 | keypoint << 5 | octave,
 //                 so the reference's stable best / second best are the two
 //                 smallest keys of the untaken candidates
@@ -70,14 +72,15 @@ ODO_INLINE int lmk_decide(uint32_t k1, uint32_t k2, float nnratio) {
 }
 
 __global__ void __launch_bounds__(256) k_lm_prior(const int32_t* __restrict__ prior, const odo_landmark* __restrict__ lms,
-                                                  int nL, const int* __restrict__ nkp, int kp_cap,
+                                                  int nL, const uint8_t* __restrict__ taken_in,
+                                                  const int* __restrict__ nkp, int kp_cap,
                                                   uint32_t* __restrict__ seen, int seen_words,
                                                   int32_t* __restrict__ prior_eff, uint8_t* __restrict__ taken0) {
     const int f = blockIdx.y, j = blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= kp_cap) return;
-    const int n = min(nkp[f + 1], kp_cap);
+    const int n = min(nkp[f], kp_cap);
     int k = (prior && j < n) ? prior[(size_t)f * kp_cap + j] : -1;
-    uint8_t tk = 0;
+    uint8_t tk = (!prior && taken_in && j < n) ? taken_in[(size_t)f * kp_cap + j] : 0;
     if (k < 0 || k >= nL) {
         k = -1;
     } else {
@@ -93,52 +96,20 @@ __global__ void __launch_bounds__(256) k_lm_prior(const int32_t* __restrict__ pr
     taken0[(size_t)f * kp_cap + j] = tk;
 }
 
-__global__ void __launch_bounds__(256) k_lm_bin(const float* __restrict__ kun, const orb_kp* __restrict__ kps,
-                                                const int* __restrict__ nkp, int kp_cap, LmGrid G,
+__global__ void __launch_bounds__(256) k_lm_bin(const float* __restrict__ kun, const int32_t* __restrict__ oct,
+                                                int oct_stride, const int* __restrict__ nkp, int kp_cap, LmGrid G,
                                                 float2* __restrict__ bxy, uint32_t* __restrict__ bjo,
                                                 int* __restrict__ cstart) {
     extern __shared__ int s_cnt[];  // ncells + 1
-    const int f = blockIdx.x, ncells = G.gx * G.gy;
-    const int n = min(nkp[f + 1], kp_cap);
-    const float* K = kun + (size_t)(f + 1) * kp_cap * 2;
-    const orb_kp* P = kps + (size_t)(f + 1) * kp_cap;
-    for (int c = threadIdx.x; c <= ncells; c += blockDim.x) s_cnt[c] = 0;
-    __syncthreads();
-    for (int j = threadIdx.x; j < n; j += blockDim.x) {
-        const int cell = lmk_cell(K[2 * j + 1] - G.y0, G.inv, G.gy) * G.gx + lmk_cell(K[2 * j] - G.x0, G.inv, G.gx);
-        atomicAdd(&s_cnt[cell], 1);
-    }
-    __syncthreads();
-    // exclusive scan by wave 0: a run of cells per lane, then the lanes' totals
-    if (threadIdx.x < 64) {
-        const int per = (ncells + 63) / 64, c0 = min((int)threadIdx.x * per, ncells), c1 = min(c0 + per, ncells);
-        int sum = 0;
-        for (int c = c0; c < c1; c++) sum += s_cnt[c];
-        int inc = sum;
-        for (int o = 1; o < 64; o <<= 1) {
-            const int t = __shfl_up(inc, o);
-            if ((int)threadIdx.x >= o) inc += t;
-        }
-        int run = inc - sum;
-        for (int c = c0; c < c1; c++) {
-            const int t = s_cnt[c];
-            s_cnt[c] = run;
-            run += t;
-        }
-        if (threadIdx.x == 63) s_cnt[ncells] = inc;
-    }
-    __syncthreads();
-    int* cs = cstart + (size_t)f * (ncells + 1);
-    for (int c = threadIdx.x; c <= ncells; c += blockDim.x) cs[c] = s_cnt[c];
-    __syncthreads();
-    // the order inside a cell is whatever the atomics give: candidates are keys
-    for (int j = threadIdx.x; j < n; j += blockDim.x) {
-        const float x = K[2 * j], y = K[2 * j + 1];
-        const int cell = lmk_cell(y - G.y0, G.inv, G.gy) * G.gx + lmk_cell(x - G.x0, G.inv, G.gx);
-        const int pos = atomicAdd(&s_cnt[cell], 1);
-        bxy[(size_t)f * kp_cap + pos] = make_float2(x, y);
-        bjo[(size_t)f * kp_cap + pos] = (uint32_t)j | ((uint32_t)(P[j].octave & 31) << 16);
-    }
+    const int f = blockIdx.x;
+    const int32_t* O = oct + (size_t)f * kp_cap * oct_stride;
+    float2* xy = bxy + (size_t)f * kp_cap;
+    uint32_t* jo = bjo + (size_t)f * kp_cap;
+    lmk_bin(kun + (size_t)f * kp_cap * 2, min(nkp[f], kp_cap), G, s_cnt, cstart + (size_t)f * (G.gx * G.gy + 1),
+            [&](int pos, int j, float x, float y) {
+                xy[pos] = make_float2(x, y);
+                jo[pos] = (uint32_t)j | ((uint32_t)(O[(size_t)j * oct_stride] & 31) << 16);
+            });
 }
 
 __global__ void __launch_bounds__(256) k_lm_cands(const float* __restrict__ Tcw, const odo_landmark* __restrict__ lms,
@@ -150,7 +121,7 @@ __global__ void __launch_bounds__(256) k_lm_cands(const float* __restrict__ Tcw,
                                                   int* __restrict__ ccount, uint32_t* __restrict__ cand) {
     extern __shared__ __attribute__((aligned(16))) uint8_t s_lm[];
     const int f = blockIdx.y, ncells = G.gx * G.gy;
-    const int n = min(nkp[f + 1], kp_cap);
+    const int n = min(nkp[f], kp_cap);
     float2* s_xy = reinterpret_cast<float2*>(s_lm);                       // kp_cap
     uint32_t* s_jo = reinterpret_cast<uint32_t*>(s_xy + kp_cap);          // kp_cap
     int* s_cs = reinterpret_cast<int*>(s_jo + kp_cap);                    // ncells + 1
@@ -168,22 +139,16 @@ __global__ void __launch_bounds__(256) k_lm_cands(const float* __restrict__ Tcw,
     const float nan = __builtin_nanf("");
     float u = nan, v = nan, ur = nan;
     bool in = false;
-    // Frame::isInFrustum, the arithmetic of k_proj_cands
+    // Frame::isInFrustum: a NaN pixel passes these bounds
     if (!(L.flags & (ODO_LM_BAD | ODO_LM_SEEN)) && !was_seen) {
-        float Pc[3];
-#pragma unroll
-        for (int k = 0; k < 3; k++)
-            Pc[k] = (float)((((double)T[4 * k] * L.X[0] + (double)T[4 * k + 1] * L.X[1]) +
-                             (double)T[4 * k + 2] * L.X[2]) + (double)T[4 * k + 3]);
-        if (!(Pc[2] < 0.0f)) {
-            const float invz = 1.0f / Pc[2];
-            const float uu = C.fx * Pc[0] * invz + C.cx;
-            const float vv = C.fy * Pc[1] * invz + C.cy;
-            if (!(uu < C.minX || uu > C.maxX) && !(vv < C.minY || vv > C.maxY)) {
+        const LmkCam Pc = lmk_camera(T, L.X);
+        if (!(Pc.z < 0.0f)) {
+            const LmkPix p = lmk_pixel_frustum(Pc, C);
+            if (!(p.u < C.minX || p.u > C.maxX) && !(p.v < C.minY || p.v > C.maxY)) {
                 in = true;
-                u = uu;
-                v = vv;
-                ur = uu - C.mbf * invz;
+                u = p.u;
+                v = p.v;
+                ur = p.ur;
             }
         }
     }
@@ -197,25 +162,19 @@ __global__ void __launch_bounds__(256) k_lm_cands(const float* __restrict__ Tcw,
         uint32_t ld[8];
 #pragma unroll
         for (int k = 0; k < 8; k++) ld[k] = reinterpret_cast<const uint32_t*>(L.desc)[k];
-        const uint8_t* D = desc + (size_t)(f + 1) * kp_cap * 32;
+        const uint8_t* D = desc + (size_t)f * kp_cap * 32;
         // candidate k of landmark i at [f][k][i]: a wave's k-th candidates share cache lines
         uint32_t* out = cand + (size_t)f * LMK_CAP * nL + i;
-        const LmkRange r = lmk_range(u, v, th, G);
-        for (int cy = r.cy0; cy <= r.cy1; cy++) {
-            const int e = s_cs[cy * G.gx + r.cx1 + 1];
-            for (int k = s_cs[cy * G.gx + r.cx0]; k < e; k++) {
-                const float2 q = s_xy[k];
-                const float dx = q.x - u, dy = q.y - v;
-                if (fabsf(dx) < th && fabsf(dy) < th) {
-                    if (c < LMK_CAP) {
-                        const uint32_t jo = s_jo[k];
-                        const int j = (int)(jo & 0xffff);
-                        out[(size_t)c * nL] = lmk_key(j, (int)(jo >> 16), lmk_hamming(ld, D + 32 * (size_t)j));
-                    }
-                    c++;
-                }
+        lmk_for_window(lmk_range(u, v, th, G), s_cs, G, 0, n, 0, 1, [&](int k) {
+            const float2 q = s_xy[k];
+            if (!lmk_in_window(q.x, q.y, u, v, th)) return;
+            if (c < LMK_CAP) {
+                const uint32_t jo = s_jo[k];
+                const int j = (int)(jo & 0xffff);
+                out[(size_t)c * nL] = lmk_key(j, (int)(jo >> 16), lmk_hamming(ld, D + 32 * (size_t)j));
             }
-        }
+            c++;
+        });
     }
     // the count, with the landmark's HAS_OBS bit so the resolver reads one word per landmark
     ccount[fi] = c < 0 ? -1 : (c | ((L.flags & ODO_LM_HAS_OBS) ? LMK_OBS : 0));
@@ -243,7 +202,7 @@ __global__ void __launch_bounds__(LMK_NT) k_lm_resolve(const odo_landmark* __res
     __shared__ int s_changed, s_nov, s_nin, s_nm, s_ne;
     const int f = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int ncells = G.gx * G.gy;
-    const int n = min(nkp[f + 1], kp_cap);
+    const int n = min(nkp[f], kp_cap);
     int* own0 = s_res;             // kp_cap
     int* own1 = own0 + kp_cap;     // kp_cap
     int* s_cs = own1 + kp_cap;     // ncells + 1
@@ -252,7 +211,7 @@ __global__ void __launch_bounds__(LMK_NT) k_lm_resolve(const odo_landmark* __res
     int32_t* chf = choice + (size_t)f * nL;
     int32_t* ovf = over + (size_t)f * nL;
     const uint8_t* tk = taken0 + (size_t)f * kp_cap;
-    const uint8_t* D = desc + (size_t)(f + 1) * kp_cap * 32;
+    const uint8_t* D = desc + (size_t)f * kp_cap * 32;
     const float2* XY = bxy + (size_t)f * kp_cap;
     const uint32_t* JO = bjo + (size_t)f * kp_cap;
     if (tid == 0) s_nov = s_nin = s_nm = s_ne = 0;
@@ -310,20 +269,14 @@ __global__ void __launch_bounds__(LMK_NT) k_lm_resolve(const odo_landmark* __res
             uint32_t ld[8];
 #pragma unroll
             for (int k = 0; k < 8; k++) ld[k] = reinterpret_cast<const uint32_t*>(lms[i].desc)[k];
-            const LmkRange r = lmk_range(u, v, th, G);
             uint32_t a1 = LMK_NONE, a2 = LMK_NONE;
-            for (int cy = r.cy0; cy <= r.cy1; cy++) {
-                const int e = s_cs[cy * G.gx + r.cx1 + 1];
-                for (int k = s_cs[cy * G.gx + r.cx0] + lane; k < e; k += 64) {
-                    const float2 p = XY[k];
-                    const float dx = p.x - u, dy = p.y - v;
-                    if (fabsf(dx) < th && fabsf(dy) < th) {
-                        const uint32_t jo = JO[k];
-                        const int j = (int)(jo & 0xffff);
-                        if (own[j] >= i) lmk_insert(lmk_key(j, (int)(jo >> 16), lmk_hamming(ld, D + 32 * (size_t)j)), a1, a2);
-                    }
-                }
-            }
+            lmk_for_window(lmk_range(u, v, th, G), s_cs, G, 0, n, lane, 64, [&](int k) {
+                const float2 p = XY[k];
+                if (!lmk_in_window(p.x, p.y, u, v, th)) return;
+                const uint32_t jo = JO[k];
+                const int j = (int)(jo & 0xffff);
+                if (own[j] >= i) lmk_insert(lmk_key(j, (int)(jo >> 16), lmk_hamming(ld, D + 32 * (size_t)j)), a1, a2);
+            });
             const uint32_t m1 = lmk_wave_min(a1);
             const uint32_t m2 = lmk_wave_min(a1 == m1 ? a2 : a1);  // keys are distinct: one lane holds m1
             if (lane == 0) {
@@ -445,9 +398,9 @@ int launch_local_map_search(hipStream_t st, const LmSearch& a) {
     if (lds_r > 64 * 1024)
         (void)hipFuncSetAttribute((const void*)k_lm_resolve, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_r);
     hipLaunchKernelGGL(k_lm_prior, dim3((a.kp_cap + 255) / 256, a.nframes), dim3(256), 0, st, a.prior, a.lms, a.nL,
-                       a.nkp, a.kp_cap, a.seen, a.seen_words, a.prior_eff, a.taken0);
-    hipLaunchKernelGGL(k_lm_bin, dim3(a.nframes), dim3(256), lds_bin, st, a.kun, a.kps, a.nkp, a.kp_cap, a.G, a.bxy,
-                       a.bjo, a.cstart);
+                       a.taken_in, a.nkp, a.kp_cap, a.seen, a.seen_words, a.prior_eff, a.taken0);
+    hipLaunchKernelGGL(k_lm_bin, dim3(a.nframes), dim3(256), lds_bin, st, a.kun, a.oct, a.oct_stride, a.nkp, a.kp_cap,
+                       a.G, a.bxy, a.bjo, a.cstart);
     if (a.nL > 0)
         hipLaunchKernelGGL(k_lm_cands, dim3((a.nL + 255) / 256, a.nframes), dim3(256), lds_c, st, a.Tcw, a.lms, a.nL,
                            a.seen, a.seen_words, a.nkp, a.kp_cap, a.desc, a.bxy, a.bjo, a.cstart, a.G, a.C, a.th,

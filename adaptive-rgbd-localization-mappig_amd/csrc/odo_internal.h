@@ -387,13 +387,11 @@ void launch_pnp_ransac(hipStream_t st, const float* Xw, const float* uv, const i
                        const float K4[4], int H, float reproj_err, double confidence, int* idx, double* model,
                        double* Rproj, uint8_t* mask, int* good, int* state, odo_pnp_ransac_result* res,
                        uint8_t* mask_out);
-int launch_projection_match(hipStream_t st, const float* Tcw, const odo_landmark* lms, int nL, const float* kun,
-                            const int32_t* octave, const uint8_t* desc, int n, const uint8_t* slot_taken,
-                            const float* calib5, const float* bounds, float th, float nnratio, float* proj,
-                            uint8_t* inview, int* ccount, uint32_t* cand, int32_t* slot_lm, int* nmatches);
-size_t projection_cand_cap();
-// Batched TrackLocalMap (k_localmap.hip), nframes frames in batch slots 1 ..
-// nframes of the arrays kun / kps / desc / nkp point at (slot 0's base).
+// The local-map search (k_localmap.hip) over nframes frames of kp_cap keypoint
+// rows each: kun / oct / desc / nkp point at the first frame searched. The
+// octave of keypoint j of frame f is oct[(f * kp_cap + j) * oct_stride]
+// (stride in 32-bit words: sizeof(orb_kp) / 4 over orb_kp rows, 1 over a
+// plain array).
 struct LmGrid {
     float x0, y0, inv;  // origin (minX, minY) and 1 / cell size of the keypoint grid
     int gx, gy;
@@ -407,10 +405,12 @@ struct LmSearch {
     const float* Tcw;            // nframes x 16
     const odo_landmark* lms;     // nL
     const int32_t* prior;        // nframes x kp_cap or null
-    const float* kun;
-    const orb_kp* kps;
-    const uint8_t* desc;
-    const int* nkp;
+    const uint8_t* taken_in;     // nframes x kp_cap or null: the taken slots of a search without a prior
+    const float* kun;            // nframes x kp_cap x 2
+    const int32_t* oct;
+    int oct_stride;
+    const uint8_t* desc;         // nframes x kp_cap x 32
+    const int* nkp;              // nframes
     LmGrid G;
     LmCalib C;
     float th, nnratio;
@@ -432,6 +432,7 @@ int local_map_cand_cap();
 LmGrid local_map_grid(const float bounds[4]);
 // prior, bins, candidates, resolve, merge and edge gather; -1: kp_cap above 8191
 int launch_local_map_search(hipStream_t st, const LmSearch& a);
+// after the batch's k_pnp; nkp is the batch's slot-0 base, as launch_pnp takes it (frame f in slot f + 1)
 void launch_local_map_stats(hipStream_t st, const odo_landmark* lms, const int* nkp, int kp_cap, const int32_t* slot_lm,
                             const uint8_t* pnp_mask, const odo_pair_result* pres, uint8_t* outlier,
                             odo_local_map_result* res, int nframes);

@@ -485,16 +485,30 @@ int odo_projection_match(odo_ctx* c, const float Tcw[16], const odo_landmark* lm
     if (n > 8191) return fail(ODO_ERR_CAPACITY, "more than 8191 keypoints");
     *n_matches = 0;
     hipStream_t st = c->stream;
-    float bounds[4];
-    odo_image_bounds(c, bounds);
+    float b[4];
+    odo_image_bounds(c, b);
     const odo_calib& k = c->cfg.calib;
-    const float cal5[5] = {k.fx, k.fy, k.cx, k.cy, k.mbf};
-    const size_t nl = std::max(nL, 1), nn = std::max(n, 1);
+    // one frame of the local-map search (k_localmap.hip): kp_cap = the frame's
+    // own rows, no prior, the caller's taken slots; scratch from the arena
+    LmSearch a{};
+    a.nframes = 1;
+    a.nL = nL;
+    a.kp_cap = std::max(n, 1);
+    a.seen_words = (nL + 31) / 32;
+    a.oct_stride = 1;
+    a.G = local_map_grid(b);
+    a.C = LmCalib{k.fx, k.fy, k.cx, k.cy, k.mbf, b[0], b[1], b[2], b[3]};
+    a.th = th;
+    a.nnratio = nn_ratio;
+    const size_t nl = std::max(nL, 1), nn = a.kp_cap, nw = std::max(a.seen_words, 1);
+    const size_t ncells = (size_t)a.G.gx * a.G.gy;
     DevArena& A = c->arena;
     A.begin();
     DevBuf dT(A, 64), dl(A, nl * sizeof(odo_landmark)), dk(A, nn * 8), doc(A, nn * 4), dd(A, nn * 32), dtk(A, nn),
-        dproj(A, nl * 12), din(A, nl), dcc(A, nl * 4), dcand(A, nl * projection_cand_cap() * 4), dsl(A, nn * 4),
-        dnm(A, 4);
+        dn(A, 4), dseen(A, nw * 4), dpe(A, nn * 4), dt0(A, nn), dbxy(A, nn * 8), dbjo(A, nn * 4),
+        dcs(A, (ncells + 1) * 4), dproj(A, nl * 12), dcc(A, nl * 4), dcand(A, nl * local_map_cand_cap() * 4),
+        dch(A, nl * 4), dov(A, nl * 4), dsl(A, nn * 4), df2(A, nn * 4), dXg(A, nn * 12),
+        dres(A, sizeof(odo_local_map_result));
     ARENA_CHECK(A);
     HIPCHK(hipMemcpyAsync(dT.p, Tcw, 64, hipMemcpyHostToDevice, st));
     if (nL) HIPCHK(hipMemcpyAsync(dl.p, lms, (size_t)nL * sizeof(odo_landmark), hipMemcpyHostToDevice, st));
@@ -503,17 +517,36 @@ int odo_projection_match(odo_ctx* c, const float Tcw[16], const odo_landmark* lm
         HIPCHK(hipMemcpyAsync(doc.p, octave, (size_t)n * 4, hipMemcpyHostToDevice, st));
         HIPCHK(hipMemcpyAsync(dd.p, desc, (size_t)n * 32, hipMemcpyHostToDevice, st));
         if (slot_taken) HIPCHK(hipMemcpyAsync(dtk.p, slot_taken, (size_t)n, hipMemcpyHostToDevice, st));
-        else HIPCHK(hipMemsetAsync(dtk.p, 0, (size_t)n, st));
     }
-    if (launch_projection_match(st, dT.as<float>(), dl.as<odo_landmark>(), nL, dk.as<float>(), doc.as<int32_t>(),
-                                dd.as<uint8_t>(), n, dtk.as<uint8_t>(), cal5, bounds, th, nn_ratio, dproj.as<float>(),
-                                din.as<uint8_t>(), dcc.as<int>(), dcand.as<uint32_t>(), dsl.as<int32_t>(),
-                                dnm.as<int>()) != 0)
-        return fail(ODO_ERR_CAPACITY, "projection match capacity");
+    HIPCHK(hipMemsetD32Async((hipDeviceptr_t)dn.p, n, 1, st));
+    HIPCHK(hipMemsetAsync(dseen.p, 0, nw * 4, st));
+    a.Tcw = dT.as<float>();
+    a.lms = dl.as<odo_landmark>();
+    a.taken_in = slot_taken ? dtk.as<uint8_t>() : nullptr;
+    a.kun = dk.as<float>();
+    a.oct = doc.as<int32_t>();
+    a.desc = dd.as<uint8_t>();
+    a.nkp = dn.as<int>();
+    a.seen = dseen.as<uint32_t>();
+    a.prior_eff = dpe.as<int32_t>();
+    a.taken0 = dt0.as<uint8_t>();
+    a.bxy = dbxy.as<float2>();
+    a.bjo = dbjo.as<uint32_t>();
+    a.cstart = dcs.as<int>();
+    a.proj = dproj.as<float>();
+    a.ccount = dcc.as<int>();
+    a.cand = dcand.as<uint32_t>();
+    a.choice = dch.as<int32_t>();
+    a.over = dov.as<int32_t>();
+    a.slot_lm = dsl.as<int32_t>();
+    a.f2_src = df2.as<int32_t>();
+    a.Xg = dXg.as<float>();
+    a.res = dres.as<odo_local_map_result>();
+    if (launch_local_map_search(st, a) != 0) return fail(ODO_ERR_CAPACITY, "projection match capacity");
     HIPCHK(hipGetLastError());
     if (nL) HIPCHK(hipMemcpyAsync(proj, dproj.p, (size_t)nL * 12, hipMemcpyDeviceToHost, st));
     if (n) HIPCHK(hipMemcpyAsync(slot_lm, dsl.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(n_matches, dnm.p, 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(n_matches, &a.res->n_matches, 4, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     return ODO_OK;
 }
@@ -665,11 +698,15 @@ int odo_track_local_map(odo_ctx* c, const odo_landmark* lms, int nL, const float
     a.Tcw = s.dev<float>(o_T);
     a.lms = s.dev<odo_landmark>(o_lms);
     a.prior = prior ? s.dev<int32_t>(o_prior) : nullptr;
-    // slot 0 of the batch's frame set: frame i sits in slot i + 1
-    a.kun = c->kun + fb * KC * 2;
-    a.kps = c->kps + fb * KC;
-    a.desc = c->desc + fb * KC * 32;
-    a.nkp = c->nkp + fb;
+    // slot 0 of the batch's frame set (k_pnp's and the statistics' base): frame i
+    // sits in slot i + 1, the search starts at slot 1
+    const float* kun0 = c->kun + fb * KC * 2;
+    const int* nkp0 = c->nkp + fb;
+    a.kun = kun0 + KC * 2;
+    a.oct = &c->kps[(fb + 1) * KC].octave;
+    a.oct_stride = sizeof(orb_kp) / 4;
+    a.desc = c->desc + (fb + 1) * KC * 32;
+    a.nkp = nkp0 + 1;
     a.G = c->lm_grid;
     a.C = LmCalib{k.fx, k.fy, k.cx, k.cy, k.mbf, b[0], b[1], b[2], b[3]};
     a.th = th;
@@ -694,10 +731,10 @@ int odo_track_local_map(odo_ctx* c, const odo_landmark* lms, int nL, const float
     // the second PnPSolver::Compute: k_pnp with pair p = frame p, its "F1
     // points" the gathered landmark positions (slot p of Xg), its F2 the
     // frame's slot p + 1, from the pose passed in
-    launch_pnp(st, L.f2_src, L.Xg, a.kun, c->ur + fb * KC, a.nkp, c->kp_cap, 0, c->cal, a.Tcw, L.ints, L.ints + c->maxb,
+    launch_pnp(st, L.f2_src, L.Xg, kun0, c->ur + fb * KC, nkp0, c->kp_cap, 0, c->cal, a.Tcw, L.ints, L.ints + c->maxb,
                0, L.edges, L.pres, L.mask, n);
     HIPCHK(hipGetLastError());
-    launch_local_map_stats(st, a.lms, a.nkp, c->kp_cap, L.slot, L.mask, L.pres, L.outl, L.res, n);
+    launch_local_map_stats(st, a.lms, nkp0, c->kp_cap, L.slot, L.mask, L.pres, L.outl, L.res, n);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(s.h, L.res, (size_t)n * sizeof(odo_local_map_result), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));

@@ -680,6 +680,55 @@ class Odometry:
         check(self.lib.odo_gicp_covariances(self.h, ptr(P), ptr(offs), len(clouds), ptr(Cv)))
         return [Cv[offs[p]:offs[p + 1]].reshape(-1, 3, 3) for p in range(len(clouds))]
 
+    def gicp_grid_batch(self, pairs, max_iterations: int = 10, max_corr_dist: float = 0.07, cell: float = 0.0):
+        """gicp_batch with the grid neighbour searches (odo_gicp_grid_batch): the
+        same results bit for bit, clouds of up to 1048576 points. cell: the grid's
+        cell edge in metres, 0 = chosen by the library."""
+        P = len(pairs)
+        so = np.zeros(P + 1, np.int32)
+        to = np.zeros(P + 1, np.int32)
+        so[1:] = np.cumsum([len(s) for s, _, _ in pairs])
+        to[1:] = np.cumsum([len(t) for _, t, _ in pairs])
+        cat = lambda xs: np.ascontiguousarray(np.concatenate([np.asarray(x, np.float32).reshape(-1, 3) for x in xs])
+                                              if xs else np.zeros((0, 3), np.float32))
+        src, tgt = cat([s for s, _, _ in pairs]), cat([t for _, t, _ in pairs])
+        g = np.ascontiguousarray(np.stack([np.eye(4, dtype=np.float32) if q is None else np.asarray(q, np.float32)
+                                           for _, _, q in pairs]) if P else np.zeros((1, 4, 4), np.float32))
+        T = np.zeros((max(P, 1), 16), np.float32)
+        conv, it, nc = (np.zeros(max(P, 1), np.int32) for _ in range(3))
+        check(self.lib.odo_gicp_grid_batch(self.h, ptr(src), ptr(so), ptr(tgt), ptr(to), ptr(g), P, max_iterations,
+                                           max_corr_dist, cell, ptr(T), ptr(conv), ptr(it), ptr(nc)))
+        return [(T[p].reshape(4, 4), int(conv[p]), int(it[p]), int(nc[p])) for p in range(P)]
+
+    def gicp_grid_covariances(self, clouds, cell: float = 0.0):
+        """gicp_covariances with the grid search (odo_gicp_grid_covariances): the
+        same arrays bit for bit."""
+        offs = np.zeros(len(clouds) + 1, np.int32)
+        offs[1:] = np.cumsum([len(c) for c in clouds])
+        P = np.ascontiguousarray(np.concatenate([np.asarray(c, np.float32).reshape(-1, 3) for c in clouds])
+                                 if clouds else np.zeros((0, 3), np.float32))
+        Cv = np.full((max(int(offs[-1]), 1), 9), np.nan)
+        check(self.lib.odo_gicp_grid_covariances(self.h, ptr(P), ptr(offs), len(clouds), cell, ptr(Cv)))
+        return [Cv[offs[p]:offs[p + 1]].reshape(-1, 3, 3) for p in range(len(clouds))]
+
+    def gicp_dense(self, pairs, guesses=None, max_iterations: int = 15, max_corr_dist: float = 0.05):
+        """GeneralizedICP::Compute(pF1, pF2, guess) (odo_gicp_dense) for a list of
+        (source frame, target frame) of the last dense_clouds call, on the clouds
+        where they lie in HBM. guesses: a list of 4x4 or None per pair, or None.
+        Returns a list of (T12, converged, iterations, n_corr)."""
+        P = len(pairs)
+        pr = np.ascontiguousarray(np.asarray(pairs, np.int32).reshape(-1, 2) if P else np.zeros((1, 2), np.int32))
+        g = None
+        if guesses is not None and P:
+            g = np.ascontiguousarray(np.stack([np.eye(4, dtype=np.float32) if q is None else np.asarray(q, np.float32)
+                                               for q in guesses]))
+            assert g.shape == (P, 4, 4)
+        T = np.zeros((max(P, 1), 16), np.float32)
+        conv, it, nc = (np.zeros(max(P, 1), np.int32) for _ in range(3))
+        check(self.lib.odo_gicp_dense(self.h, ptr(pr), P, None if g is None else ptr(g), max_iterations,
+                                      max_corr_dist, ptr(T), ptr(conv), ptr(it), ptr(nc)))
+        return [(T[p].reshape(4, 4), int(conv[p]), int(it[p]), int(nc[p])) for p in range(P)]
+
     def timings(self):
         ms = np.zeros(16, np.float32)
         names = (C.c_char_p * 16)()

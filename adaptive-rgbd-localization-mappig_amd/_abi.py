@@ -212,6 +212,9 @@ SIGNATURES = {
     "odo_gicp_batch": (C.c_int, [P, P, P, P, P, P, C.c_int, C.c_int, C.c_double, P, P, P, P]),
     "odo_gicp": (C.c_int, [P, P, C.c_int, P, C.c_int, P, C.c_int, C.c_double, P, P, P, P]),
     "odo_gicp_covariances": (C.c_int, [P, P, P, C.c_int, P]),
+    "odo_gicp_grid_batch": (C.c_int, [P, P, P, P, P, P, C.c_int, C.c_int, C.c_double, C.c_float, P, P, P, P]),
+    "odo_gicp_grid_covariances": (C.c_int, [P, P, P, C.c_int, C.c_float, P]),
+    "odo_gicp_dense": (C.c_int, [P, P, C.c_int, P, C.c_int, C.c_double, P, P, P, P]),
     "odo_rng_seed": (None, [P, C.c_uint32]),
     "odo_rng_next": (C.c_int32, [P]),
     "odo_debug_pyramid": (C.c_int, [P, C.c_int, P, C.c_size_t]),

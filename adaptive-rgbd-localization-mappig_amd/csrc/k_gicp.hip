@@ -15,12 +15,23 @@
 //               as thread-strided partial sums, the four waves' partials of a
 //               lane position added in order, an xor butterfly read on lane 0
 //               (oracle/gicp_ref.cpp's sum256), and the convergence test.
+// Whole clouds (GeneralizedICP::Compute(pF1, pF2, guess), generalizedicp.cpp:
+// 41-53; odo_gicp_grid_batch, odo_gicp_dense) run the same code over a uniform
+// grid per cloud instead of the two brute-force scans, with the scans' results
+// bit for bit (DESIGN §4 "Dense GICP"):
+//   k_gg_*           bounds, cell keys and a counting sort of every cloud into
+//                    cell-ordered (x, y, z, index) rows plus cell starts;
+//   k_gicp_cov_grid  the 20 neighbours by (distance, index) over Chebyshev rings
+//                    of cells, stopped by gg_ring_bound; then cov_finish;
+//   k_gicp_grid      k_gicp's body with the correspondence search over the cells
+//                    within max_corr_dist of the query.
 // The restatement, its pinned choices and the oracle are in oracle/gicp_ref.cpp
 // (PCL is absent: parity with the library is unpinned).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cfloat>
+#include <cstring>
 
 #include "odo_internal.h"
 #include "odo_linalg.h"
@@ -48,36 +59,11 @@ __device__ __forceinline__ float dist2f(const float* a, const float* b) {
     return r;
 }
 
-// computeCovariances for point q of a cloud P of n points (LDS or global)
-__device__ __forceinline__ void cov_point(const float* __restrict__ P, int n, int q, double eps,
-                                          double* __restrict__ C) {
-    // the sorted top 20 in registers: +inf padding stands for "fewer than 20
-    // so far", a candidate is inserted after equal distances (ties to the lower
-    // index, as the scan is in index order)
-    float nd[GI_K];
-    int nn[GI_K];
-#pragma unroll
-    for (int j = 0; j < GI_K; j++) {
-        nd[j] = __builtin_inff();
-        nn[j] = 0;
-    }
-    const float pq[3] = {P[3 * q], P[3 * q + 1], P[3 * q + 2]};
-    for (int i = 0; i < n; i++) {
-        const float pi[3] = {P[3 * i], P[3 * i + 1], P[3 * i + 2]};
-        const float d = dist2f(pq, pi);
-        if (!(d < nd[GI_K - 1])) continue;
-#pragma unroll
-        for (int j = GI_K - 1; j > 0; j--) {
-            const bool up = d < nd[j - 1];
-            const bool here = !up && d < nd[j];
-            nd[j] = up ? nd[j - 1] : (here ? d : nd[j]);
-            nn[j] = up ? nn[j - 1] : (here ? i : nn[j]);
-        }
-        if (d < nd[0]) {
-            nd[0] = d;
-            nn[0] = i;
-        }
-    }
+// computeCovariances from the ordered neighbour list nn[20] of point q on:
+// mean and covariance in double, eigenvalues replaced by (1, 1, eps). One piece
+// of code for the brute-force and the grid selection.
+__device__ __forceinline__ void cov_finish(const float* __restrict__ P, const int* nn, int q, double eps,
+                                           double* __restrict__ C) {
     double mean[3] = {0, 0, 0}, cov[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
     for (int j = 0; j < GI_K; j++) {
         const float* pt = P + 3 * nn[j];
@@ -115,6 +101,40 @@ __device__ __forceinline__ void cov_point(const float* __restrict__ P, int n, in
     }
 #pragma unroll
     for (int k = 0; k < 9; k++) C[9 * q + k] = out[k];
+}
+
+// computeCovariances for point q of a cloud P of n points (LDS or global): the
+// brute-force selection of the 20 neighbours, then cov_finish
+__device__ __forceinline__ void cov_point(const float* __restrict__ P, int n, int q, double eps,
+                                          double* __restrict__ C) {
+    // the sorted top 20 in registers: +inf padding stands for "fewer than 20
+    // so far", a candidate is inserted after equal distances (ties to the lower
+    // index, as the scan is in index order)
+    float nd[GI_K];
+    int nn[GI_K];
+#pragma unroll
+    for (int j = 0; j < GI_K; j++) {
+        nd[j] = __builtin_inff();
+        nn[j] = 0;
+    }
+    const float pq[3] = {P[3 * q], P[3 * q + 1], P[3 * q + 2]};
+    for (int i = 0; i < n; i++) {
+        const float pi[3] = {P[3 * i], P[3 * i + 1], P[3 * i + 2]};
+        const float d = dist2f(pq, pi);
+        if (!(d < nd[GI_K - 1])) continue;
+#pragma unroll
+        for (int j = GI_K - 1; j > 0; j--) {
+            const bool up = d < nd[j - 1];
+            const bool here = !up && d < nd[j];
+            nd[j] = up ? nd[j - 1] : (here ? d : nd[j]);
+            nn[j] = up ? nn[j - 1] : (here ? i : nn[j]);
+        }
+        if (d < nd[0]) {
+            nd[0] = d;
+            nn[0] = i;
+        }
+    }
+    cov_finish(P, nn, q, eps, C);
 }
 
 // grid (point blocks, problems, 2): z = 0 the target clouds, z = 1 the sources
@@ -615,35 +635,33 @@ __device__ __forceinline__ int nn_search(const float* __restrict__ T, int n, con
     return best;
 }
 
-// one workgroup per problem of the batch
-__global__ __launch_bounds__(GI_THREADS) void k_gicp(const float* __restrict__ src, const float* __restrict__ tgt,
-                                                   const double* __restrict__ Cs, const double* __restrict__ Ct,
-                                                   float* __restrict__ outp, double* __restrict__ Mah,
-                                                   int* __restrict__ is, int* __restrict__ it, GicpArgs A,
-                                                   float* __restrict__ T12, int* __restrict__ outi) {
+struct BruteSearch {
+    const float* tgt;
+    int nt;
+    __device__ __forceinline__ int operator()(const float* q, float* bd) const { return nn_search(tgt, nt, q, bd); }
+};
+
+// computeTransformation of one problem on its workgroup. Every pointer is the
+// problem's own (source, target and their covariances; outp, Mah, is, it sized
+// by the source). The correspondence search is the policy: search(q, &d)
+// returns the target point nearest to q, the lowest index among equals, and
+// its float squared distance (+inf when it looked at no point).
+template <class Search>
+__device__ __forceinline__ void gicp_body(const float* __restrict__ src, int ns, const float* __restrict__ tgt,
+                                          int nt, const double* __restrict__ Cs, const double* __restrict__ Ct,
+                                          float* __restrict__ outp, double* __restrict__ Mah, int* __restrict__ is,
+                                          int* __restrict__ it, const float* __restrict__ guess,
+                                          double max_corr_dist, int max_iterations, int max_inner,
+                                          float* __restrict__ T12, int* __restrict__ outi, const Search& search) {
     __shared__ double red[GI_NV][GI_THREADS];
     __shared__ double bc[GI_NV];
     __shared__ int wcnt[GI_WAVES];
     const int lane = threadIdx.x & (GI_LANES - 1), wave = threadIdx.x / GI_LANES;
-    const int pb = blockIdx.x;
-    const int s0 = A.soffs[pb], t0 = A.toffs[pb];
-    const int ns = A.soffs[pb + 1] - s0, nt = A.toffs[pb + 1] - t0;
-    const float* guess = A.guess + 16 * pb;
-    T12 += 16 * pb;
-    outi += 4 * pb;
     if (ns < 20 || nt < 20) {  // generalizedicp.cpp:33
         if (threadIdx.x < 16) T12[threadIdx.x] = threadIdx.x % 5 == 0 ? 1.f : 0.f;
         if (threadIdx.x < 4) outi[threadIdx.x] = 0;
         return;
     }
-    src += 3 * (size_t)s0;
-    outp += 3 * (size_t)s0;
-    Cs += 9 * (size_t)s0;
-    Mah += 9 * (size_t)s0;
-    is += s0;
-    it += s0;
-    tgt += 3 * (size_t)t0;
-    Ct += 9 * (size_t)t0;
     for (int i = threadIdx.x; i < ns; i += GI_THREADS) {  // transformPointCloud(output, output, guess)
         const float p0 = src[3 * i], p1 = src[3 * i + 1], p2 = src[3 * i + 2];
 #pragma unroll
@@ -654,7 +672,7 @@ __global__ __launch_bounds__(GI_THREADS) void k_gicp(const float* __restrict__ s
     float Tcur[16], Tprev[16];
 #pragma unroll
     for (int i = 0; i < 16; i++) Tcur[i] = Tprev[i] = i % 5 == 0 ? 1.f : 0.f;
-    const double dist_threshold = A.max_corr_dist * A.max_corr_dist;
+    const double dist_threshold = max_corr_dist * max_corr_dist;
     int nr_iterations = 0, conv = 0, ncorr = 0;
     while (!conv) {
         double R[9];
@@ -677,7 +695,7 @@ __global__ __launch_bounds__(GI_THREADS) void k_gicp(const float* __restrict__ s
                 float q[3];
                 xform4f(Tcur, pi, q);
                 float bd;
-                best = nn_search(tgt, nt, q, &bd);  // (an LDS-staged target measured no faster)
+                best = search(q, &bd);  // (brute force: an LDS-staged target measured no faster)
                 if ((double)bd < dist_threshold) {
                     hit = true;
                     const double* C1 = Cs + 9 * i;
@@ -739,8 +757,8 @@ __global__ __launch_bounds__(GI_THREADS) void k_gicp(const float* __restrict__ s
 #pragma unroll
             for (int k = 0; k < 6; k++) gn += bf.gradient[k] * bf.gradient[k];
             result = sqrt(gn) < 1e-2 ? ST_SUCCESS : ST_RUNNING;
-        } while (result == ST_RUNNING && inner < A.max_inner);
-        if (!(result == ST_NO_PROGRESS || result == ST_SUCCESS || inner == A.max_inner)) break;
+        } while (result == ST_RUNNING && inner < max_inner);
+        if (!(result == ST_NO_PROGRESS || result == ST_SUCCESS || inner == max_inner)) break;
         apply_state(x, Tcur);
         double delta = 0.;
 #pragma unroll
@@ -752,7 +770,7 @@ __global__ __launch_bounds__(GI_THREADS) void k_gicp(const float* __restrict__ s
                 if (c_delta > delta) delta = c_delta;
             }
         nr_iterations++;
-        if (nr_iterations >= A.max_iterations || delta < 1) {
+        if (nr_iterations >= max_iterations || delta < 1) {
             conv = 1;
 #pragma unroll
             for (int i = 0; i < 16; i++) Tprev[i] = Tcur[i];
@@ -770,7 +788,324 @@ __global__ __launch_bounds__(GI_THREADS) void k_gicp(const float* __restrict__ s
     }
 }
 
+// one workgroup per problem of the batch
+__global__ __launch_bounds__(GI_THREADS) void k_gicp(const float* __restrict__ src, const float* __restrict__ tgt,
+                                                   const double* __restrict__ Cs, const double* __restrict__ Ct,
+                                                   float* __restrict__ outp, double* __restrict__ Mah,
+                                                   int* __restrict__ is, int* __restrict__ it, GicpArgs A,
+                                                   float* __restrict__ T12, int* __restrict__ outi) {
+    const int pb = blockIdx.x;
+    const int s0 = A.soffs[pb], t0 = A.toffs[pb];
+    const int ns = A.soffs[pb + 1] - s0, nt = A.toffs[pb + 1] - t0;
+    tgt += 3 * (size_t)t0;
+    gicp_body(src + 3 * (size_t)s0, ns, tgt, nt, Cs + 9 * (size_t)s0, Ct + 9 * (size_t)t0, outp + 3 * (size_t)s0,
+              Mah + 9 * (size_t)s0, is + s0, it + s0, A.guess + 16 * pb, A.max_corr_dist, A.max_iterations,
+              A.max_inner, T12 + 16 * pb, outi + 4 * pb, BruteSearch{tgt, nt});
+}
+
+// ------------------------------------------------------------------ the grid
+// (DESIGN §4 "Dense GICP"; GgCloud in odo_internal.h)
+constexpr int GG_CHUNK = 4096;  // cells per scan workgroup, points per bounds workgroup
+
+// floats as uint32 whose order is the floats' order (bounds by atomicMin / Max)
+__device__ __forceinline__ uint32_t gg_encode(float f) {
+    const uint32_t b = __float_as_uint(f);
+    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+
+__device__ __forceinline__ void gg_cell3(const GgCloud& g, const float* p, int* c) {
+    const int dim[3] = {g.gx, g.gy, g.gz};
+#pragma unroll
+    for (int a = 0; a < 3; a++) {
+        const float t = (p[a] - g.mn[a]) * g.inv;
+        c[a] = (int)fminf(fmaxf(floorf(t), 0.f), (float)(dim[a] - 1));  // outside (a query): clipped
+    }
+}
+
+// grid (point blocks, clouds)
+__global__ __launch_bounds__(256) void k_gg_pack(const float* __restrict__ src, int stride,
+                                                 const int* __restrict__ row0, const int* __restrict__ offs,
+                                                 float* __restrict__ dst) {
+    const int k = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= offs[k + 1] - offs[k]) return;
+    const float* s = src + (size_t)stride * ((size_t)row0[k] + i);
+    float* d = dst + 3 * ((size_t)offs[k] + i);
+    d[0] = s[0];
+    d[1] = s[1];
+    d[2] = s[2];
+}
+
+// grid (GG_CHUNK-point blocks, clouds): min and max are exact in any order
+__global__ __launch_bounds__(256) void k_gg_bounds(const float* __restrict__ P, const int* __restrict__ offs,
+                                                   uint32_t* __restrict__ bounds) {
+    const int k = blockIdx.y, n = offs[k + 1] - offs[k];
+    const int i0 = blockIdx.x * GG_CHUNK;
+    if (i0 >= n) return;
+    const float* Pk = P + 3 * (size_t)offs[k];
+    float mn[3] = {__builtin_inff(), __builtin_inff(), __builtin_inff()};
+    float mx[3] = {-__builtin_inff(), -__builtin_inff(), -__builtin_inff()};
+    const int i1 = min(n, i0 + GG_CHUNK);
+    for (int i = i0 + threadIdx.x; i < i1; i += 256)
+#pragma unroll
+        for (int a = 0; a < 3; a++) {
+            const float v = Pk[3 * (size_t)i + a];
+            mn[a] = fminf(mn[a], v);
+            mx[a] = fmaxf(mx[a], v);
+        }
+#pragma unroll
+    for (int a = 0; a < 3; a++)
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) {
+            mn[a] = fminf(mn[a], __shfl_xor(mn[a], o, GI_LANES));
+            mx[a] = fmaxf(mx[a], __shfl_xor(mx[a], o, GI_LANES));
+        }
+    if ((threadIdx.x & (GI_LANES - 1)) == 0)
+#pragma unroll
+        for (int a = 0; a < 3; a++) {
+            atomicMin(&bounds[6 * k + a], gg_encode(mn[a]));
+            atomicMax(&bounds[6 * k + 3 + a], gg_encode(mx[a]));
+        }
+}
+
+// grid (point blocks, clouds): the cell of every point and the cells' counts
+__global__ __launch_bounds__(256) void k_gg_count(const float* __restrict__ P, const GgCloud* __restrict__ cl,
+                                                  int* __restrict__ key, int* __restrict__ cnt) {
+    const GgCloud g = cl[blockIdx.y];
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= g.n) return;
+    const size_t row = (size_t)g.p0 + i;
+    const float p[3] = {P[3 * row], P[3 * row + 1], P[3 * row + 2]};
+    int c[3];
+    gg_cell3(g, p, c);
+    const int cell = (c[2] * g.gy + c[1]) * g.gx + c[0];
+    key[row] = cell;
+    atomicAdd(&cnt[g.c0 + cell], 1);
+}
+
+// exclusive scan in place of this thread's items [begin, end) within the
+// workgroup's; returns the workgroup's total
+__device__ int gg_block_scan(int* __restrict__ a, int begin, int end) {
+    __shared__ int ws[256];
+    int s = 0;
+    for (int i = begin; i < end; i++) s += a[i];
+    ws[threadIdx.x] = s;
+    __syncthreads();
+    for (int o = 1; o < 256; o <<= 1) {
+        const int v = (int)threadIdx.x >= o ? ws[threadIdx.x - o] : 0;
+        __syncthreads();
+        ws[threadIdx.x] += v;
+        __syncthreads();
+    }
+    int run = ws[threadIdx.x] - s;
+    for (int i = begin; i < end; i++) {
+        const int v = a[i];
+        a[i] = run;
+        run += v;
+    }
+    return ws[255];
+}
+
+// the counting sort's scan over the m entries of all clouds: chunks, the chunk
+// totals (one workgroup), and the totals added back
+__global__ __launch_bounds__(256) void k_gg_scan_chunks(int* __restrict__ a, int m, int* __restrict__ bsum) {
+    const int per = GG_CHUNK / 256;
+    const int begin = min(m, (int)blockIdx.x * GG_CHUNK + (int)threadIdx.x * per), end = min(m, begin + per);
+    const int tot = gg_block_scan(a, begin, end);
+    if (threadIdx.x == 0) bsum[blockIdx.x] = tot;
+}
+__global__ __launch_bounds__(256) void k_gg_scan_tops(int* __restrict__ bsum, int nb) {
+    const int per = (nb + 255) / 256;
+    const int begin = min(nb, (int)threadIdx.x * per), end = min(nb, begin + per);
+    (void)gg_block_scan(bsum, begin, end);
+}
+__global__ __launch_bounds__(256) void k_gg_scan_add(int* __restrict__ a, int m, const int* __restrict__ bsum) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < m) a[i] += bsum[i / GG_CHUNK];
+}
+
+// grid (point blocks, clouds): the order within a cell is the atomics' (no
+// result depends on it: every selection compares (distance, index))
+__global__ __launch_bounds__(256) void k_gg_scatter(const float* __restrict__ P, const GgCloud* __restrict__ cl,
+                                                    const int* __restrict__ key, const int* __restrict__ cstart,
+                                                    int* __restrict__ fill, float4* __restrict__ sorted) {
+    const GgCloud g = cl[blockIdx.y];
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= g.n) return;
+    const size_t row = (size_t)g.p0 + i;
+    const int cell = g.c0 + key[row];
+    const int pos = cstart[cell] + atomicAdd(&fill[cell], 1);
+    sorted[pos] = make_float4(P[3 * row], P[3 * row + 1], P[3 * row + 2], __int_as_float(i));
+}
+
+// grid (point blocks, clouds): one lane per point, in cell order, so that a
+// wave walks the same cells. The top 20 by (distance, index) over Chebyshev
+// rings around the point's cell, until the 20th distance held is below what
+// any unseen point can have (gg_ring_bound) or the rings have covered the grid.
+__global__ __launch_bounds__(64) void k_gicp_cov_grid(const float* __restrict__ P, const GgCloud* __restrict__ cl,
+                                                      const int* __restrict__ cstart,
+                                                      const float4* __restrict__ sorted, double* __restrict__ C,
+                                                      double eps) {
+    const GgCloud g = cl[blockIdx.y];
+    const int s = blockIdx.x * 64 + threadIdx.x;
+    if (g.n < 20 || s >= g.n) return;
+    const float4 me = sorted[(size_t)g.p0 + s];
+    const float pq[3] = {me.x, me.y, me.z};
+    int c[3];
+    gg_cell3(g, pq, c);
+    // as cov_point: +inf padding, whose index 0 no candidate goes below
+    float nd[GI_K];
+    int nn[GI_K];
+#pragma unroll
+    for (int j = 0; j < GI_K; j++) {
+        nd[j] = __builtin_inff();
+        nn[j] = 0;
+    }
+    const int* cs = cstart + g.c0;
+    const int rmax = max(max(max(c[0], g.gx - 1 - c[0]), max(c[1], g.gy - 1 - c[1])), max(c[2], g.gz - 1 - c[2]));
+    for (int r = 0;; r++) {
+        const int z0 = max(c[2] - r, 0), z1 = min(c[2] + r, g.gz - 1);
+        const int y0 = max(c[1] - r, 0), y1 = min(c[1] + r, g.gy - 1);
+        const int x0 = max(c[0] - r, 0), x1 = min(c[0] + r, g.gx - 1);
+        for (int z = z0; z <= z1; z++)
+            for (int y = y0; y <= y1; y++) {
+                const int row = (z * g.gy + y) * g.gx;
+                // a row on the shell's z or y faces is one run of cells, any
+                // other row has the shell's two x faces
+                const bool full = abs(z - c[2]) == r || abs(y - c[1]) == r;
+                for (int k = 0; k < 2; k++) {
+                    int xa = x0, xb = x1;
+                    if (full) {
+                        if (k) break;
+                    } else {
+                        xa = xb = k ? c[0] + r : c[0] - r;
+                        if (xa < 0 || xa > g.gx - 1) continue;
+                    }
+                    const int e = cs[row + xb + 1];
+                    for (int i = cs[row + xa]; i < e; i++) {
+                        const float4 t = sorted[i];
+                        const float pi[3] = {t.x, t.y, t.z};
+                        const int idx = __float_as_int(t.w);
+                        const float d = dist2f(pq, pi);
+#define GG_LT(j) (d < nd[j] || (d == nd[j] && idx < nn[j]))
+                        if (!GG_LT(GI_K - 1)) continue;
+#pragma unroll
+                        for (int j = GI_K - 1; j > 0; j--) {
+                            const bool up = GG_LT(j - 1);
+                            const bool here = !up && GG_LT(j);
+                            nd[j] = up ? nd[j - 1] : (here ? d : nd[j]);
+                            nn[j] = up ? nn[j - 1] : (here ? idx : nn[j]);
+                        }
+                        if (GG_LT(0)) {
+                            nd[0] = d;
+                            nn[0] = idx;
+                        }
+#undef GG_LT
+                    }
+                }
+            }
+        if (r >= rmax || (double)nd[GI_K - 1] < gg_ring_bound(g.w, g.slack, r)) break;
+    }
+    cov_finish(P + 3 * (size_t)g.p0, nn, __float_as_int(me.w), eps, C + 9 * (size_t)g.p0);
+}
+
+// the correspondence search over g.rings rings around the query's (clipped)
+// cell: every target point closer than max_corr_dist lies in them (the host
+// chose g.rings so), the selection is by (distance, index)
+struct GridSearch {
+    GgCloud g;
+    const int* cs;
+    const float4* sorted;
+    __device__ __forceinline__ int operator()(const float* q, float* bdo) const {
+        int c[3];
+        gg_cell3(g, q, c);
+        float bd = __builtin_inff();
+        int best = 0;
+        const int z0 = max(c[2] - g.rings, 0), z1 = min(c[2] + g.rings, g.gz - 1);
+        const int y0 = max(c[1] - g.rings, 0), y1 = min(c[1] + g.rings, g.gy - 1);
+        const int x0 = max(c[0] - g.rings, 0), x1 = min(c[0] + g.rings, g.gx - 1);
+        for (int z = z0; z <= z1; z++)
+            for (int y = y0; y <= y1; y++) {
+                const int row = (z * g.gy + y) * g.gx;
+                const int e = cs[row + x1 + 1];
+                for (int i = cs[row + x0]; i < e; i++) {
+                    const float4 t = sorted[i];
+                    const float tj[3] = {t.x, t.y, t.z};
+                    const float d = dist2f(q, tj);
+                    const int idx = __float_as_int(t.w);
+                    if (d < bd || (d == bd && idx < best)) {
+                        bd = d;
+                        best = idx;
+                    }
+                }
+            }
+        *bdo = bd;
+        return best;
+    }
+};
+
+// one workgroup per pair; the clouds of a pair by index, so that a cloud serves
+// many pairs with one grid and one set of covariances
+__global__ __launch_bounds__(GI_THREADS) void k_gicp_grid(
+    const float* __restrict__ P, const GgCloud* __restrict__ cl, const GgPair* __restrict__ pairs,
+    const int* __restrict__ cstart, const float4* __restrict__ sorted, const double* __restrict__ C,
+    float* __restrict__ outp, double* __restrict__ Mah, int* __restrict__ is, int* __restrict__ it,
+    const float* __restrict__ guess, double max_corr_dist, int max_iterations, int max_inner, float* __restrict__ T12,
+    int* __restrict__ outi) {
+    const int pb = blockIdx.x;
+    const GgPair pr = pairs[pb];
+    const GgCloud S = cl[pr.s], T = cl[pr.t];
+    const size_t w = (size_t)pr.work;
+    gicp_body(P + 3 * (size_t)S.p0, S.n, P + 3 * (size_t)T.p0, T.n, C + 9 * (size_t)S.p0, C + 9 * (size_t)T.p0,
+              outp + 3 * w, Mah + 9 * w, is + w, it + w, guess + 16 * pb, max_corr_dist, max_iterations, max_inner,
+              T12 + 16 * pb, outi + 4 * pb, GridSearch{T, cstart + T.c0, sorted});
+}
+
 }  // namespace
+
+float gg_decode(uint32_t u) {
+    const uint32_t b = (u & 0x80000000u) ? (u & 0x7fffffffu) : ~u;
+    float f;
+    memcpy(&f, &b, 4);
+    return f;
+}
+
+void launch_gg_pack(hipStream_t st, const float* src, int stride, const int* row0, const int* offs, int ncl,
+                    int max_n, float* dst) {
+    if (ncl == 0 || max_n == 0) return;
+    hipLaunchKernelGGL(k_gg_pack, dim3((max_n + 255) / 256, ncl), dim3(256), 0, st, src, stride, row0, offs, dst);
+}
+
+void launch_gg_bounds(hipStream_t st, const float* P, const int* offs, int ncl, int max_n, uint32_t* bounds) {
+    if (ncl == 0 || max_n == 0) return;
+    hipLaunchKernelGGL(k_gg_bounds, dim3((max_n + GG_CHUNK - 1) / GG_CHUNK, ncl), dim3(256), 0, st, P, offs, bounds);
+}
+
+void launch_gg_build(hipStream_t st, const float* P, const GgCloud* cl, int ncl, int max_n, int64_t ncells_total,
+                     int* key, int* cnt, int* fill, int* bsum, float4* sorted) {
+    if (ncl == 0 || max_n == 0) return;
+    const dim3 pts((max_n + 255) / 256, ncl);
+    const int m = (int)ncells_total + 1, nb = (m + GG_CHUNK - 1) / GG_CHUNK;
+    hipLaunchKernelGGL(k_gg_count, pts, dim3(256), 0, st, P, cl, key, cnt);
+    hipLaunchKernelGGL(k_gg_scan_chunks, dim3(nb), dim3(256), 0, st, cnt, m, bsum);
+    hipLaunchKernelGGL(k_gg_scan_tops, dim3(1), dim3(256), 0, st, bsum, nb);
+    hipLaunchKernelGGL(k_gg_scan_add, dim3((m + 255) / 256), dim3(256), 0, st, cnt, m, bsum);
+    hipLaunchKernelGGL(k_gg_scatter, pts, dim3(256), 0, st, P, cl, key, cnt, fill, sorted);
+}
+
+void launch_gg_cov(hipStream_t st, const float* P, const GgCloud* cl, int ncl, int max_n, const int* cstart,
+                   const float4* sorted, double* C) {
+    if (ncl == 0 || max_n < 20) return;
+    hipLaunchKernelGGL(k_gicp_cov_grid, dim3((max_n + 63) / 64, ncl), dim3(64), 0, st, P, cl, cstart, sorted, C, 1e-3);
+}
+
+void launch_gg_icp(hipStream_t st, const float* P, const GgCloud* cl, const GgPair* pairs, int nprob,
+                   const int* cstart, const float4* sorted, const double* C, float* outp, double* Mah, int* is,
+                   int* it, const float* guess, double max_corr_dist, int max_iterations, int max_inner, float* T12,
+                   int* outi) {
+    if (nprob == 0) return;
+    hipLaunchKernelGGL(k_gicp_grid, dim3(nprob), dim3(GI_THREADS), 0, st, P, cl, pairs, cstart, sorted, C, outp, Mah,
+                       is, it, guess, max_corr_dist, max_iterations, max_inner, T12, outi);
+}
 
 void launch_gicp_cov(hipStream_t st, const float* src, const int* soffs, double* Cs, const float* tgt,
                      const int* toffs, double* Ct, int nprob, int max_n) {

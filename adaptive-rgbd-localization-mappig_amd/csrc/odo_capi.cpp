@@ -55,6 +55,7 @@ static void free_ctx(odo_ctx* c) {
     if (c->ba_dev) (void)hipFree(c->ba_dev);
     if (c->fuse_dev) (void)hipFree(c->fuse_dev);
     free_dense_clouds(c);
+    free_gicp_grid(c);
     free_hyp_session(c->hs);
     c->pool.release();
     free_ricp(c);

@@ -312,6 +312,11 @@ struct odo_ctx {
     size_t cloud_cap = 0, cloud_out_cap = 0, cloud_counts_at = 0;
     int cloud_n = -1;
     std::vector<int32_t> cloud_off, cloud_np;
+    // the grid GICP entry points (odo_gicp_grid_batch, odo_gicp_grid_covariances,
+    // odo_gicp_dense): the point-sized block and the cell-sized block, each
+    // allocated by the first call and regrown when a call needs more
+    uint8_t *gg_pts = nullptr, *gg_cells = nullptr;
+    size_t gg_pts_cap = 0, gg_cells_cap = 0;
     // sequence state: the last tracked batch sits in frame set seq_set (its
     // last frame at slot seq_n); getters read view_set / view_n
     bool has_prev = false;
@@ -447,6 +452,7 @@ int run_knn(odo_ctx* c, hipStream_t st, int s, int n);  // k_vo_lm + launch_set_
 int run_pair_match(odo_ctx* c, hipStream_t st, int set, int n, bool first_valid, bool latched);
 void free_local_map(odo_ctx* c);               // odo_stages.cpp
 void free_dense_clouds(odo_ctx* c);            // odo_cloud.cpp
+void free_gicp_grid(odo_ctx* c);               // odo_gicp_grid.cpp
 void free_hyp_session(HypSession* h);          // odo_hyps.cpp
 
 // One packed round trip of a synchronous entry point. The sections are laid

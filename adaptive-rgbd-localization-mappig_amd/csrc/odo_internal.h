@@ -359,6 +359,55 @@ void launch_gicp(hipStream_t st, const float* src, const float* tgt, int nprob, 
 // its rows of Cs / Ct are not written); max_n = the longest cloud of either side
 void launch_gicp_cov(hipStream_t st, const float* src, const int* soffs, double* Cs, const float* tgt,
                      const int* toffs, double* Ct, int nprob, int max_n);
+// Dense GICP (k_gicp.hip; DESIGN §4 "Dense GICP"): the neighbour searches over
+// a uniform grid per cloud. The clouds of a call lie packed (x, y, z) one after
+// the other in P; cloud k is points [p0, p0 + n). Its grid has gx * gy * gz
+// cells (x fastest), cell (i, j, k) = floorf((p - mn) * inv) per axis, clamped;
+// cstart[c0 + cell] is the first row of the cell in `sorted` (x, y, z, index
+// within the cloud as int bits), rows of all clouds in one sequence, so
+// cstart[c0 + ncells] is the cloud's end and the next cloud's first cell.
+constexpr int GG_MAX_POINTS = 1 << 20;      // points per cloud
+constexpr int64_t GG_MAX_CELLS = 1 << 24;   // cells per cloud (the table budget)
+constexpr int64_t GG_MAX_TOTAL_CELLS = 1 << 28;  // cells of all clouds of a call
+struct GgCloud {
+    int p0, n, c0;
+    int gx, gy, gz;
+    float mn[3], inv;
+    // the stop rule: after Chebyshev ring r every unseen point has a float
+    // squared distance of at least gg_ring_bound(w, slack, r)
+    double w, slack;
+    int rings;  // ICP: rings searched around the query's cell
+};
+// the stop rule's bound; one definition for the host (rings) and the kernels
+__host__ __device__ inline double gg_ring_bound(double w, double slack, int r) {
+    const double g = r * w - slack;
+    return g > 0 ? g * g * (1.0 - 0x1p-20) - 0x1p-140 : 0.0;
+}
+// a problem of the grid ICP: clouds by index, `work` the first row of its own
+// outp / Mah / is / it (sized by the source)
+struct GgPair {
+    int s, t, work;
+};
+// cloud k: x, y, z of rows [row0[k], ...) of `stride` floats at src into the
+// packed rows [offs[k], offs[k + 1]) of dst (row0, offs on the device)
+void launch_gg_pack(hipStream_t st, const float* src, int stride, const int* row0, const int* offs, int ncl,
+                    int max_n, float* dst);
+// bounds[6 * k]: min x, y, z and max x, y, z of cloud k as ordered uint32
+// (gg_decode), preset to 0xffffffff / 0 by the caller; offs ncl + 1 (device)
+void launch_gg_bounds(hipStream_t st, const float* P, const int* offs, int ncl, int max_n, uint32_t* bounds);
+float gg_decode(uint32_t u);
+// counting sort of every cloud by cell: cnt and fill (ncells_total + 1 each) are
+// preset to 0; cnt becomes cstart, bsum holds (ncells_total + 1 + 4095) / 4096 ints
+void launch_gg_build(hipStream_t st, const float* P, const GgCloud* cl, int ncl, int max_n, int64_t ncells_total,
+                     int* key, int* cnt, int* fill, int* bsum, float4* sorted);
+// computeCovariances of every cloud of >= 20 points: C 9 per point, in point order
+void launch_gg_cov(hipStream_t st, const float* P, const GgCloud* cl, int ncl, int max_n, const int* cstart,
+                   const float4* sorted, double* C);
+// k_gicp with the grid correspondence search, one workgroup per pair
+void launch_gg_icp(hipStream_t st, const float* P, const GgCloud* cl, const GgPair* pairs, int nprob,
+                   const int* cstart, const float4* sorted, const double* C, float* outp, double* Mah, int* is,
+                   int* it, const float* guess, double max_corr_dist, int max_iterations, int max_inner, float* T12,
+                   int* outi);
 // Batched ADAPTIVE_RICP / RANSAC back-ends (k_ricp.hip), on the pair stream
 // after launch_ransac. The branch rule's constants (odometry.cpp:52-53):
 struct RicpCfg {

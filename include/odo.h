@@ -341,7 +341,8 @@ int odo_pnp_ransac_batch(odo_ctx* ctx, const float* Xw, const float* uv, const i
  * iterations run, n_corr = correspondences of the last one. Covariances,
  * correspondences and the BFGS all run on the GPU (k_gicp.hip); neighbour
  * searches are brute force, so clouds hold at most 16384 points
- * (ODO_ERR_CAPACITY; RANSAC's matched clouds are a few hundred). */
+ * (ODO_ERR_CAPACITY; RANSAC's matched clouds are a few hundred; whole clouds
+ * go through odo_gicp_grid_batch or odo_gicp_dense). */
 int odo_gicp(odo_ctx* ctx, const float* src, int ns, const float* tgt, int nt, const float guess[16],
              int max_iterations, double max_corr_dist, float T12[16], int* converged, int* iterations, int* n_corr);
 
@@ -365,6 +366,38 @@ int odo_gicp_batch(odo_ctx* ctx, const float* src, const int32_t* soffs, const f
  * the target set differs from it in any bit. At most 16384 points per cloud
  * (ODO_ERR_CAPACITY). */
 int odo_gicp_covariances(odo_ctx* ctx, const float* P, const int32_t* offs, int nprob, double* C);
+
+/* odo_gicp_batch with grid neighbour searches (DESIGN §4 "Dense GICP"): every
+ * cloud is binned into a uniform grid, the 20 covariance neighbours are found
+ * over Chebyshev rings of cells and the ICP correspondence in the cells within
+ * max_corr_dist of the query, with the results of the brute-force scans bit for
+ * bit (T12, converged, iterations, n_corr equal odo_gicp_batch's on any pair
+ * that accepts). A cloud holds at most 1048576 points (a 640 x 480 cloud with
+ * leaf 0 fits), a call 32767 pairs and 2^29 points (ODO_ERR_CAPACITY).
+ * cell: edge of the grid's cells in metres. 0 = chosen per cloud by the
+ * library: max(extent / cbrt(8 n), slightly above max_corr_dist), extent the
+ * cloud's longest side, n its points; then the ICP search is the 27 cells
+ * around the query. The cell is doubled until the cloud's table fits 2^24
+ * cells; no result depends on the cell. cell > 0 = forced (tests): a table
+ * above 2^24 cells, or above 2^28 cells over the clouds of a call, is
+ * ODO_ERR_CAPACITY; a cell below max_corr_dist widens the ICP search to about
+ * ceil(max_corr_dist / cell) rings. A cloud that spans more than FLT_MAX on
+ * an axis is held in one cell (a forced cell: ODO_ERR_CAPACITY). A transformed
+ * source point outside the
+ * target's grid is searched from the nearest cell; beyond max_corr_dist it has
+ * no correspondence, as in the brute-force search.
+ * ODO_ERR_ARG (nothing written): null pointers with non-zero sizes, offsets
+ * not starting at 0 or decreasing, max_iterations < 1, max_corr_dist or cell
+ * negative or not finite, a non-finite guess entry or coordinate, nprob < 0. */
+int odo_gicp_grid_batch(odo_ctx* ctx, const float* src, const int32_t* soffs, const float* tgt,
+                        const int32_t* toffs, const float* guesses, int nprob, int max_iterations,
+                        double max_corr_dist, float cell, float* T12, int32_t* converged, int32_t* iterations,
+                        int32_t* n_corr);
+/* odo_gicp_covariances with the grid search: C equals it bit for bit on any
+ * cloud it accepts. Every cloud has one role, so there is no source / target
+ * echo check. cell as above (0: max_corr_dist counts as 0); at most 65535
+ * clouds of 1048576 points and 2^29 points per call (ODO_ERR_CAPACITY). */
+int odo_gicp_grid_covariances(odo_ctx* ctx, const float* P, const int32_t* offs, int nprob, float cell, double* C);
 
 /* ---- Trajectory (host only) ----
  * Relative-pose chain of the batched contract: results[i].Tcw is frame i's
@@ -615,9 +648,32 @@ int odo_dense_clouds_host(odo_ctx* ctx, const uint8_t* bgr, const uint16_t* dept
  * ODO_ERR_STATE before any dense-cloud call; ODO_ERR_ARG: i outside the last
  * call's frames, cap < 0, a null pts with cap > 0, a null n. */
 int odo_get_dense_cloud(odo_ctx* ctx, int i, odo_cloud_point* pts, int32_t* counts, int cap, int* n);
-/* The same buffers where they lie in HBM (what a device-side
- * GeneralizedICP::Compute(pF1, pF2, guess), generalizedicp.cpp:41-53, would
- * read), valid until the next dense-cloud call or odo_destroy. d_counts may be
+/* GeneralizedICP(max_iterations, max_corr_dist)::Compute(pF1, pF2, guess)
+ * (generalizedicp.cpp:41-53, 65-89; the reference runs it as GeneralizedICP(15,
+ * 0.05) on VoxelGridFilterCloud(0.03f) clouds) for nprob pairs of frames of the
+ * last dense-cloud call, read where they lie in HBM (x, y, z at the 16-byte
+ * stride of odo_cloud_point): pairs[2p] = source frame, pairs[2p+1] = target
+ * frame; guesses 16 per pair or NULL (identity). It registers whatever the
+ * buffers hold: with Twc == NULL in odo_dense_clouds that is the reference's
+ * camera-frame registration, with a Twc the clouds in the map frame. The grid
+ * and the covariances are built once per distinct frame named in pairs, so a
+ * chain (i - 1, i), (i, i + 1) pays for frame i once. Results as
+ * odo_gicp_grid_batch on the same points, bit for bit (automatic cell); an
+ * empty cloud or one under 20 points: converged 0, identity. Synchronises the
+ * context first; its scratch is allocated by the first call and regrown when a
+ * call needs more (a context that never calls it allocates nothing for it).
+ * ODO_ERR_STATE before any dense-cloud call; ODO_ERR_ARG (nothing written):
+ * nprob < 0, null pointers with nprob > 0, a frame outside the last
+ * dense-cloud call, max_iterations < 1, max_corr_dist negative or not finite,
+ * a non-finite guess entry; ODO_ERR_CAPACITY: more than 65535 pairs or frames
+ * in the dense-cloud call, or 2^29 points over the distinct frames;
+ * ODO_ERR_DEVICE: a named cloud holds a non-finite coordinate (odo_dense_clouds
+ * with finite Twc produces none). nprob == 0 is valid. */
+int odo_gicp_dense(odo_ctx* ctx, const int32_t* pairs, int nprob, const float* guesses, int max_iterations,
+                   double max_corr_dist, float* T12, int32_t* converged, int32_t* iterations, int32_t* n_corr);
+/* The same buffers where they lie in HBM (what odo_gicp_dense, the device-side
+ * GeneralizedICP::Compute(pF1, pF2, guess), generalizedicp.cpp:41-53, reads),
+ * valid until the next dense-cloud call or odo_destroy. d_counts may be
  * NULL. Errors as odo_get_dense_cloud. */
 int odo_dense_cloud_device(odo_ctx* ctx, int i, const odo_cloud_point** d_pts, const int32_t** d_counts, int* n);
 

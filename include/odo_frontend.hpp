@@ -672,6 +672,25 @@ public:
               "GeneralizedICP::Compute");
         return converged != 0;
     }
+    // Compute(pF1, pF2, guess) (generalizedicp.cpp:41-53) over the frames' dense
+    // clouds (Frame::CreateCloud / VoxelGridFilterCloud), camera frame: false
+    // without running when either cloud is empty (generalizedicp.cpp:43). Whole
+    // clouds go through the grid neighbour searches (odo_gicp_grid_batch).
+    bool Compute(const Frame* pF1, const Frame* pF2, const Pose& guess) {
+        if (pF1->mpCloud.empty() || pF2->mpCloud.empty()) return false;
+        std::vector<float> pts[2];
+        const Frame* fr[2] = {pF1, pF2};
+        for (int k = 0; k < 2; ++k) {
+            pts[k].reserve(3 * fr[k]->mpCloud.size());
+            for (const odo_cloud_point& p : fr[k]->mpCloud) pts[k].insert(pts[k].end(), {p.x, p.y, p.z});
+        }
+        const int32_t so[2] = {0, (int32_t)fr[0]->mpCloud.size()}, to[2] = {0, (int32_t)fr[1]->mpCloud.size()};
+        int32_t converged = 0, iters = 0, ncorr = 0;
+        Check(odo_gicp_grid_batch(detail::shared_ctx(), pts[0].data(), so, pts[1].data(), to, guess.data(), 1, mIters,
+                                  mDist, 0.0f, mT12.data(), &converged, &iters, &ncorr),
+              "GeneralizedICP::Compute");
+        return converged != 0;
+    }
     void SetMaximumIterations(int iters) { mIters = iters; }
     void SetMaxCorrespondenceDistance(double dist) { mDist = dist; }
 

@@ -305,9 +305,9 @@ int odo_pnp_ransac(odo_ctx* c, const float* Xw, const float* uv, int n, const od
                    int32_t* good_counts) {
     if (!c || n < 0 || (n && (!Xw || !uv)) || !res) return fail(ODO_ERR_ARG, "bad pnp_ransac args");
     if (!(confidence > 0.0 && confidence < 1.0)) return fail(ODO_ERR_ARG, "confidence must be in (0, 1)");
-    memset(res, 0, sizeof(*res));
-    res->best_iter = -1;
     if (n < 10) {  // pnpransac.cpp:30: return 0 before solvePnPRansac
+        memset(res, 0, sizeof(*res));
+        res->best_iter = -1;
         if (inlier_mask && n) memset(inlier_mask, 0, (size_t)n);
         return ODO_OK;
     }

@@ -315,7 +315,20 @@ int odo_pnp_motion_ba(odo_ctx* ctx, const float* Xw, const float* obs, int n, co
  * the RANSAC inliers (Frame::SetInlier); good_counts (iterations, optional):
  * inliers of every hypothesis, of which the first res->iterations_visited are
  * the ones RANSAC visited. Hypotheses, EPnP, counts, the ordered fold and the
- * Levenberg-Marquardt refinement all run on the GPU (k_pnpransac.hip). */
+ * Levenberg-Marquardt refinement all run on the GPU (k_pnpransac.hip).
+ * Arguments: iterations < 1 runs one hypothesis (ptsetreg.cpp: niters =
+ * MAX(maxIters, 1)), so good_counts holds max(iterations, 1) entries.
+ * Refused with ODO_ERR_ARG: a null ctx / res / Xw / uv (points may be null
+ * when n = 0), n < 0, confidence not in (0, 1) (NaN included: run()'s
+ * CV_Assert); with ODO_ERR_CAPACITY: more than 65536 points, or
+ * max(iterations, 1) x points above 2^28. A refused call writes none of its
+ * outputs. reproj_err and the points are NOT validated, as in OpenCV, whose
+ * findInliers tests err <= (float)(reproj_err * reproj_err): a NaN
+ * reproj_err accepts nothing (ok = 0 after all iterations), 0 accepts only
+ * an exactly zero error, a negative value acts as its magnitude. A
+ * non-finite landmark or observation is never an inlier, and a hypothesis
+ * drawn on one counts no inliers; every device loop has a fixed trip count,
+ * so such input costs time only. */
 #define ODO_PNP_RANSAC_THROW (-1)
 int odo_pnp_ransac(odo_ctx* ctx, const float* Xw, const float* uv, int n, const odo_calib* calib, int iterations,
                    float reproj_err, double confidence, odo_pnp_ransac_result* res, uint8_t* inlier_mask,
@@ -325,7 +338,12 @@ int odo_pnp_ransac(odo_ctx* ctx, const float* Xw, const float* uv, int n, const 
  * contract of odo_track_batch): problem p = observations [offs[p], offs[p+1])
  * of Xw / uv (offs[0] = 0, nprob + 1 entries); res[p] as odo_pnp_ransac
  * (problems with fewer than 10 observations: ok = 0, best_iter = -1);
- * inlier_mask (optional) over all offs[nprob] observations. */
+ * inlier_mask (optional) over all offs[nprob] observations. nprob = 0
+ * returns ODO_OK and writes nothing. Refused with ODO_ERR_ARG, besides what
+ * odo_pnp_ransac refuses: nprob < 0, a null offs, offs[0] != 0, decreasing
+ * offsets; with ODO_ERR_CAPACITY: more than 65535 problems, a problem of more
+ * than 65536 points, max(iterations, 1) x offs[nprob] above 2^28. A refused
+ * call writes none of its outputs. */
 int odo_pnp_ransac_batch(odo_ctx* ctx, const float* Xw, const float* uv, const int32_t* offs, int nprob,
                          const odo_calib* calib, int iterations, float reproj_err, double confidence,
                          odo_pnp_ransac_result* res, uint8_t* inlier_mask);

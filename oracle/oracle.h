@@ -174,8 +174,13 @@ int oracle_pnp(const float* Xw, const float* obs, int n, const odo_calib* c,
  * confidence, inliers) of OpenCV 3.4 restated in pnpransac_ref.cpp. Xw n x 3,
  * uv n x 2 (mvKeysUn). model_out: best RANSAC model (rvec, tvec); rt_out: the
  * refined (rvec, tvec); Tcw: Converter::toHomogeneous(r, t); mask: RANSAC
- * inlier mask (n); good_counts (optional, >= iterations): inliers of every
- * visited hypothesis. Returns 1 (bOK), 0 when n < 10 or no model, -1 when
+ * inlier mask (n); good_counts (optional, max(iterations, 1) entries: iterations <= 0
+ * runs one hypothesis, ptsetreg.cpp's MAX(maxIters, 1)): inliers of every
+ * visited hypothesis. reproj_err and the points are not validated, as in
+ * OpenCV: the threshold is (float)(reproj_err^2) and a point is an inlier
+ * when err <= threshold, so NaN accepts nothing, 0 only an exact zero error
+ * and a negative value acts as its magnitude; a non-finite point is never an
+ * inlier and a hypothesis drawn on it counts nothing. Returns 1 (bOK), 0 when n < 10 or no model, -1 when
  * the refinement's cvFindExtrinsicCameraParams2 would throw (non-planar
  * inliers, only 5 of them: its DLT branch asserts count >= 6; model, mask and
  * n_inliers are set, rt_out and Tcw are zero). */

@@ -1147,7 +1147,8 @@ int oracle_pnp_ransac(const float* Xw, const float* uv, int n, const odo_calib* 
             cur[i] = e <= thr;
             good += cur[i];
         }
-        if (good_counts && iter < iterations) good_counts[iter] = good;
+        // MAX(maxIters, 1) hypotheses exist: iterations <= 0 still runs (and records) one
+        if (good_counts && iter < (iterations > 1 ? iterations : 1)) good_counts[iter] = good;
         if (good > (maxGoodCount > modelPoints - 1 ? maxGoodCount : modelPoints - 1)) {
             std::swap(cur, best);
             memcpy(bestModel, model, sizeof(bestModel));

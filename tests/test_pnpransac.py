@@ -16,31 +16,13 @@ starts where solvePnP(useExtrinsicGuess = false) starts (pnpransac.cpp:34):
 cvFindExtrinsicCameraParams2's DLT, or its homography branch for coplanar
 landmarks (test_gpu_parity_planar).
 """
-import math
-
 import numpy as np
 import pytest
 from scipy.spatial.transform import Rotation
 
 import oracle_lib as O
 from conftest import load_pkg, sequence
-
-
-def _problem(seed, n, outlier_frac, noise=0.5, planar=False):
-    rng = np.random.default_rng(seed)
-    cal = O.fr1_calib()
-    Xc = np.c_[rng.uniform(-2, 2, n), rng.uniform(-1.5, 1.5, n), rng.uniform(1, 5, n)]
-    if planar:
-        Xc[:, 2] = 3.0 + 0.2 * Xc[:, 0]
-    rv = rng.normal(0, 0.2, 3)
-    t = rng.normal(0, 0.3, 3)
-    R = Rotation.from_rotvec(rv).as_matrix()
-    Xw = (Xc - t) @ R  # Xc = R Xw + t
-    uv = np.c_[cal.fx * Xc[:, 0] / Xc[:, 2] + cal.cx, cal.fy * Xc[:, 1] / Xc[:, 2] + cal.cy]
-    uv += rng.normal(0, noise, uv.shape)
-    out = rng.random(n) < outlier_frac
-    uv[out] += rng.uniform(-80, 80, (out.sum(), 2))
-    return Xw.astype(np.float32), uv.astype(np.float32), cal, rv, t, out
+from pnpransac_cases import _cvrng_py, _five_inliers, _problem, _update_py
 
 
 def _frames_problem(nf=1000):
@@ -59,29 +41,10 @@ def _frames_problem(nf=1000):
 
 
 # ----------------------------------------------------------------- CPU
-def _cvrng_py(state, a, b, n):
-    out = []
-    for _ in range(n):
-        state = ((state & 0xFFFFFFFF) * 4164903690 + (state >> 32)) & ((1 << 64) - 1)
-        out.append(a + (state & 0xFFFFFFFF) % (b - a))
-    return out
-
-
 def test_cvrng_stream():
     got = np.zeros(64, np.int32)
     O.lib().oracle_cvrng_stream((1 << 64) - 1, 0, 97, 64, O.ptr(got))
     assert got.tolist() == _cvrng_py((1 << 64) - 1, 0, 97, 64)
-
-
-def _update_py(p, ep, m, maxit):
-    p = min(max(p, 0.0), 1.0)
-    ep = min(max(ep, 0.0), 1.0)
-    num = max(1.0 - p, 2.2250738585072014e-308)
-    denom = 1.0 - (1.0 - ep) ** m
-    if denom < 2.2250738585072014e-308:
-        return 0
-    num, denom = math.log(num), math.log(denom)
-    return maxit if denom >= 0 or -num >= maxit * (-denom) else int(round(num / denom))
 
 
 @pytest.mark.parametrize("ep", [0.0, 0.05, 0.3, 0.5, 0.7, 0.9, 0.99, 1.0])
@@ -175,16 +138,6 @@ def test_extrinsic_init_exact(planar, n):
     O.lib().oracle_pnp_refine(O.ptr(M), O.ptr(m), n, O.ptr(K), O.ptr(p))
     np.testing.assert_allclose(p[:3], rv, atol=1e-4)
     np.testing.assert_allclose(p[3:], t, atol=1e-4)
-
-
-def _five_inliers(seed):
-    """12 observations, 5 exact and 7 moved 40-120 px: the best RANSAC model
-    has exactly 5 inliers (goodCount > modelPoints - 1 accepts it)."""
-    Xw, uv, cal, *_ = _problem(seed, 12, 0.0, noise=0.0)
-    rng = np.random.default_rng(seed + 1000)
-    ang = rng.uniform(0, 2 * np.pi, 7)
-    uv[5:] += (np.c_[np.cos(ang), np.sin(ang)] * rng.uniform(40, 120, (7, 1))).astype(np.float32)
-    return Xw, uv, cal
 
 
 def test_oracle_five_inliers_dlt_asserts():

@@ -679,7 +679,6 @@ static inline int ba_nchunks(int nl, int* chunk) {
     *chunk = ch;
     return std::max(1, (nl + ch - 1) / ch);
 }
-static inline size_t ba_al(size_t b) { return (b + 255) & ~(size_t)255; }
 
 struct BaScratch {
     double *P[2], *X[2], *info, *c2, *W, *Hll, *bl, *Hinv, *Hpp, *bp, *posemax, *Sp, *S, *dx, *pchi, *pscale, *pmax, *scal;
@@ -690,11 +689,10 @@ struct BaScratch {
 };
 static BaScratch ba_carve(uint8_t* base, int nk, int nl, int ne, int nf) {
     BaScratch s{};
-    size_t off = 0;
+    Pack pk;
     auto take = [&](size_t b) {
-        uint8_t* p = base ? base + off : nullptr;
-        off += ba_al(std::max<size_t>(b, 8));
-        return p;
+        const size_t o = pk.add(std::max<size_t>(b, 8));
+        return base ? base + o : nullptr;
     };
     const size_t n = 6 * (size_t)nf;
     int chunk;
@@ -726,7 +724,7 @@ static BaScratch ba_carve(uint8_t* base, int nk, int nl, int ne, int nf) {
     s.flist = (int2*)take((size_t)ne * sizeof(int2));
     s.fcnt = (int*)take((size_t)nl * sizeof(int));
     s.cnt = (int*)take(4 * sizeof(int));
-    s.bytes = off;
+    s.bytes = pk.off;
     return s;
 }
 size_t ba_scratch_bytes(int nk, int nl, int ne, int nf) { return ba_carve(nullptr, nk, nl, ne, nf).bytes; }

@@ -1921,10 +1921,6 @@ static int ransac_rawcap(const RansacCfg& cfg) {
     return (int)((w + 63) / 64 * 64);
 }
 
-struct Layout {
-    size_t gpts, st, hyp, samples, ready, masks, raw, open, lslab, total;
-};
-
 // k_ransac_lanes grid: workgroups of LN_WAVES waves (ODO_RANSAC_LANES, at
 // least 1). 384 = 1.5 per CU
 // of the 256: alone the launch is faster at 2 per CU (512), but in the
@@ -1952,57 +1948,41 @@ static int ln_min_open() {
     return r;
 }
 
-static Layout layout(int npairs, int match_cap, int mask_words, const RansacCfg& cfg) {
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t hc = ransac_hcap(cfg);
-    Layout L;
-    size_t o = 0;
-    L.gpts = o;
-    o = al(o + (size_t)npairs * match_cap * sizeof(GoodPt));
-    L.st = o;
-    o = al(o + (size_t)npairs * sizeof(RState));
-    L.hyp = o;
-    o = al(o + (size_t)npairs * hc * sizeof(HypRes));
-    L.samples = o;
-    o = al(o + (size_t)npairs * hc * SREC * sizeof(int));
-    L.ready = o;
-    o = al(o + (size_t)npairs * hc * sizeof(int));
-    L.masks = o;
-    o = al(o + (size_t)npairs * hc * mask_words * 4);
-    L.raw = o;
-    o = al(o + (size_t)npairs * ransac_rawcap(cfg) * 4);
-    L.open = o;
-    o = al(o + (size_t)(npairs + 4) * 4);
-    L.lslab = o;  // per-wave inlier-set buffers of k_ransac_lanes (never launched for one pair:
-                  // a lone pair starts every hypothesis row in the first launch)
-    if (npairs > 1) o = al(o + (size_t)ln_groups() * LN_WAVES * 2 * mask_words * 64 * 4);
-    L.total = o;
-    return L;
-}
-
-size_t ransac_scratch_bytes(int npairs, int match_cap, int mask_words, const RansacCfg& cfg) {
-    return layout(npairs, match_cap, mask_words, cfg).total;
-}
-
-static RansacBufs carve(void* scratch, int npairs, int match_cap, int mask_words, const RansacCfg& cfg) {
-    const Layout L = layout(npairs, match_cap, mask_words, cfg);
-    char* s = (char*)scratch;
+// The scratch block's sections. A null `scratch` only measures: *bytes is the
+// block's size either way.
+static RansacBufs carve(void* scratch, int npairs, int match_cap, int mask_words, const RansacCfg& cfg,
+                        size_t* bytes = nullptr) {
+    const size_t np = (size_t)npairs, hc = ransac_hcap(cfg);
+    Pack pk;
+    auto take = [&](size_t b) {
+        const size_t o = pk.add(b);
+        return scratch ? (char*)scratch + o : nullptr;
+    };
     RansacBufs B{};
-    B.gpts = (GoodPt*)(s + L.gpts);
-    B.st = (RState*)(s + L.st);
-    B.hyp = (HypRes*)(s + L.hyp);
-    B.samples = (int*)(s + L.samples);
-    B.ready = (int*)(s + L.ready);
-    B.masks = (uint32_t*)(s + L.masks);
-    B.open_list = (int*)(s + L.open);
-    B.open_cnt = B.open_list + npairs;
-    B.lslab = (uint32_t*)(s + L.lslab);
-    B.raw = (uint32_t*)(s + L.raw);
+    B.gpts = (GoodPt*)take(np * match_cap * sizeof(GoodPt));
+    B.st = (RState*)take(np * sizeof(RState));
+    B.hyp = (HypRes*)take(np * hc * sizeof(HypRes));
+    B.samples = (int*)take(np * hc * SREC * sizeof(int));
+    B.ready = (int*)take(np * hc * sizeof(int));
+    B.masks = (uint32_t*)take(np * hc * mask_words * 4);
+    B.raw = (uint32_t*)take(np * ransac_rawcap(cfg) * 4);
+    B.open_list = (int*)take((np + 4) * 4);
+    if (scratch) B.open_cnt = B.open_list + npairs;
+    // per-wave inlier-set buffers of k_ransac_lanes (never launched for one pair: a lone
+    // pair starts every hypothesis row in the first launch, and the slab has no bytes)
+    B.lslab = (uint32_t*)take(npairs > 1 ? (size_t)ln_groups() * LN_WAVES * 2 * mask_words * 64 * 4 : 0);
     B.hcap = ransac_hcap(cfg);
     B.rawcap = ransac_rawcap(cfg);
     B.match_cap = match_cap;
     B.mask_words = mask_words;
+    if (bytes) *bytes = pk.off;
     return B;
+}
+
+size_t ransac_scratch_bytes(int npairs, int match_cap, int mask_words, const RansacCfg& cfg) {
+    size_t bytes;
+    carve(nullptr, npairs, match_cap, mask_words, cfg, &bytes);
+    return bytes;
 }
 
 // A^k of the generator's 31x31 transition (mod 2^32), host side

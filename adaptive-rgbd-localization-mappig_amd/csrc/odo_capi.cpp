@@ -17,23 +17,12 @@ int odo::sync_all(odo_ctx* c) {
 }
 
 int odo::stage_reserve(odo_ctx* c, size_t bytes) {
-    if (bytes <= c->stage_cap) return ODO_OK;
-    size_t cap = std::max(bytes, std::max(c->stage_cap * 2, (size_t)1 << 20));
-    if (c->stage_h) (void)hipHostFree(c->stage_h);
-    c->stage_h = nullptr;
-    c->stage_cap = 0;
-    if (hipHostMalloc((void**)&c->stage_h, cap, hipHostMallocDefault) != hipSuccess)
-        return fail(ODO_ERR_DEVICE, "hipHostMalloc (staging) failed");
-    c->stage_cap = cap;
-    return ODO_OK;
+    // this buffer's own policy: at least doubled, at least 1 MiB
+    return c->stage.reserve(bytes, std::max(c->stage.cap * 2, (size_t)1 << 20), "staging");
 }
 
 // ADAPTIVE_RICP scratch (odo_set_odometry): a pair's cloud has at most match_cap
 // points; sizes as launch_gicp documents them
-static void free_ricp(odo_ctx* c) {
-    for (auto& R : c->rb) R.pool.release();
-    c->ricp_alloc = false;
-}
 static int alloc_ricp(odo_ctx* c) {
     const size_t B = (size_t)c->maxb, N = B * c->match_cap;
     int e;
@@ -46,26 +35,6 @@ static int alloc_ricp(odo_ctx* c) {
         if ((e = P.alloc(&R.offs, B + 1)) || (e = P.alloc(&R.branch, B)) || (e = P.alloc(&R.rec, B))) return e;
     }
     return ODO_OK;
-}
-
-// Frees exactly what exists (also a context whose creation failed half-way)
-static void free_ctx(odo_ctx* c) {
-    if (!c) return;
-    free_local_map(c);
-    if (c->ba_dev) (void)hipFree(c->ba_dev);
-    if (c->fuse_dev) (void)hipFree(c->fuse_dev);
-    free_dense_clouds(c);
-    free_gicp_grid(c);
-    free_hyp_session(c->hs);
-    c->pool.release();
-    free_ricp(c);
-    for (hipEvent_t ev : c->events) hipEventDestroy(ev);
-    if (c->stage_h) (void)hipHostFree(c->stage_h);
-    if (c->hyp_stage_h) (void)hipHostFree(c->hyp_stage_h);
-    for (hipStream_t st : c->owned) hipStreamDestroy(st);
-    if (c->h_open) (void)hipHostFree(c->h_open);
-    if (c->latch_set_h) (void)hipHostFree(c->latch_set_h);
-    delete c;
 }
 
 static int alloc_buffers(odo_ctx* c) {
@@ -249,12 +218,12 @@ odo_ctx* odo_create(const odo_config* cfg, int device) {
     for (int i = 0; i < 2 && ok; i++) ok = mkev(&c->ev_in_copied[i]) && mkev(&c->ev_in_free[i]);
     if (!ok) {
         fail(ODO_ERR_DEVICE, "hipStreamCreate failed");
-        free_ctx(c);
+        delete c;
         return nullptr;
     }
     c->rcfg = ransac_cfg(cfg->ransac, cfg->forms);
     if (build_geometry(c) != ODO_OK || alloc_buffers(c) != ODO_OK) {
-        free_ctx(c);
+        delete c;
         return nullptr;
     }
     upload_extract_constants();
@@ -266,7 +235,7 @@ odo_ctx* odo_create(const odo_config* cfg, int device) {
     return c;
 }
 
-void odo_destroy(odo_ctx* ctx) { free_ctx(ctx); }
+void odo_destroy(odo_ctx* ctx) { delete ctx; }
 
 void* odo_stream(odo_ctx* ctx) { return ctx ? (void*)ctx->stream : nullptr; }
 
@@ -312,12 +281,10 @@ int odo_set_odometry(odo_ctx* c, int mode, const odo_ricp_params* p) {
         return fail(ODO_ERR_CAPACITY, "ricp: more than 16384 points in a cloud");
     int e;
     if ((e = sync_all(c))) return e;
-    if (mode == ODO_ODOMETRY_ADAPTIVE_RICP && !c->ricp_alloc) {
-        if ((e = alloc_ricp(c))) {  // all or nothing: the mode stays as it was, a later switch allocates afresh
-            free_ricp(c);
-            return e;
-        }
-        c->ricp_alloc = true;
+    if (mode == ODO_ODOMETRY_ADAPTIVE_RICP && c->rb[0].pool.slots.empty() && (e = alloc_ricp(c))) {
+        // all or nothing: the mode stays as it was, a later switch allocates afresh
+        for (auto& R : c->rb) R.pool.release();
+        return e;
     }
     c->ricp = rp;
     c->odo_mode = mode;
@@ -438,7 +405,7 @@ int odo_get_frame(odo_ctx* c, int i, orb_kp* kps, uint8_t* desc, float* kps_un, 
     const size_t o_n = pk.add(sizeof(int)), o_k = pk.add(KC * sizeof(orb_kp)), o_d = pk.add(KC * 32),
                  o_u = pk.add(KC * 8), o_x = pk.add(KC * 12), o_r = pk.add(KC * 4);
     if ((e = stage_reserve(c, pk.off))) return e;
-    uint8_t* h = c->stage_h;
+    uint8_t* h = c->stage.p;
     hipStream_t st = c->stream;
     HIPCHK(hipMemcpyAsync(h + o_n, f.nkp, sizeof(int), hipMemcpyDeviceToHost, st));
     if (kps) HIPCHK(hipMemcpyAsync(h + o_k, f.kps, KC * sizeof(orb_kp), hipMemcpyDeviceToHost, st));
@@ -552,22 +519,18 @@ int odo_debug_select(odo_ctx* c, const uint32_t* in, int n, int nth, int mode, u
         return ODO_OK;
     }
     if (nth > n) nth = n;
-    void* d = nullptr;
-    const size_t bytes = (size_t)n * 12 + 16;
-    HIPCHK(hipMalloc(&d, bytes));
-    uint32_t* A = (uint32_t*)d;
+    c->arena.begin();
+    DevBuf d(c->arena, (size_t)n * 12 + 16);
+    ARENA_CHECK(c->arena);
+    uint32_t* A = d.as<uint32_t>();
     int* posL = (int*)(A + n);
     int* posR = posL + n;
     int* dn = posR + n;
-    hipError_t er = hipMemcpy(A, in, (size_t)n * 4, hipMemcpyHostToDevice);
-    if (er == hipSuccess) {
-        launch_adapt_select_dbg(c->stream, A, n, nth, mode, posL, posR, dn);
-        er = hipStreamSynchronize(c->stream);
-    }
-    if (er == hipSuccess) er = hipMemcpy(out, A, (size_t)n * 4, hipMemcpyDeviceToHost);
-    if (er == hipSuccess) er = hipMemcpy(n_out, dn, sizeof(int), hipMemcpyDeviceToHost);
-    hipFree(d);
-    if (er != hipSuccess) return fail(ODO_ERR_DEVICE, hipGetErrorString(er));
+    HIPCHK(hipMemcpy(A, in, (size_t)n * 4, hipMemcpyHostToDevice));
+    launch_adapt_select_dbg(c->stream, A, n, nth, mode, posL, posR, dn);
+    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipMemcpy(out, A, (size_t)n * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(n_out, dn, sizeof(int), hipMemcpyDeviceToHost));
     return ODO_OK;
 }
 
@@ -616,15 +579,14 @@ int odo_debug_sort(odo_ctx* c, const odo_dmatch* in, int n, odo_dmatch* out) {
         memcpy(&bits, &in[i].distance, 4);
         el[i] = ((uint64_t)(uint32_t)i << 32) | bits;  // SortEl{key = distance bits, val = index}
     }
-    void* d = nullptr;
-    HIPCHK(hipMalloc(&d, (size_t)n * 8));
-    hipError_t e = hipMemcpy(d, el.data(), (size_t)n * 8, hipMemcpyHostToDevice);
-    if (e == hipSuccess && launch_sort_dbg(c->stream, d, n) != 0) e = hipErrorInvalidValue;
-    if (e == hipSuccess) e = hipGetLastError();
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e == hipSuccess) e = hipMemcpy(el.data(), d, (size_t)n * 8, hipMemcpyDeviceToHost);
-    hipFree(d);
-    if (e != hipSuccess) return fail(ODO_ERR_DEVICE, std::string("debug sort: ") + hipGetErrorString(e));
+    c->arena.begin();
+    DevBuf d(c->arena, (size_t)n * 8);
+    ARENA_CHECK(c->arena);
+    HIPCHK(hipMemcpy(d.p, el.data(), (size_t)n * 8, hipMemcpyHostToDevice));
+    if (launch_sort_dbg(c->stream, d.p, n) != 0) return fail(ODO_ERR_DEVICE, "debug sort: the launch refused its arguments");
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipMemcpy(el.data(), d.p, (size_t)n * 8, hipMemcpyDeviceToHost));
     for (int i = 0; i < n; i++) out[i] = in[(uint32_t)(el[i] >> 32)];
     return ODO_OK;
 }

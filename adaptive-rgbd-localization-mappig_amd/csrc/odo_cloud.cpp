@@ -8,28 +8,6 @@ static_assert(sizeof(odo_cloud_point) == 16 && sizeof(odo_cloud_info) == 60, "od
 
 namespace odo {
 
-void free_dense_clouds(odo_ctx* c) {
-    if (c->cloud_dev) (void)hipFree(c->cloud_dev);
-    if (c->cloud_out) (void)hipFree(c->cloud_out);
-    c->cloud_dev = c->cloud_out = nullptr;
-    c->cloud_cap = c->cloud_out_cap = 0;
-    c->cloud_n = -1;
-}
-
-// grow-only device block
-static int grow(uint8_t** p, size_t* cap, size_t bytes, const char* what) {
-    if (bytes <= *cap) return ODO_OK;
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-    *cap = 0;
-    if (hipMalloc((void**)p, bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(ODO_ERR_DEVICE, std::string(what) + ": hipMalloc failed");
-    }
-    *cap = bytes;
-    return ODO_OK;
-}
-
 static int check_args(odo_ctx* c, const void* a, const void* b, int n, float leaf, const float* Twc, odo_cloud_info* info) {
     if (!c || !a || !b || !info || n <= 0 || n > c->maxb) return fail(ODO_ERR_ARG, "bad dense_clouds args");
     if (!(leaf >= 0.0f) || !std::isfinite(leaf)) return fail(ODO_ERR_ARG, "dense_clouds: leaf must be finite and >= 0");
@@ -57,9 +35,9 @@ static int run_clouds(odo_ctx* c, const uint8_t* d_bgr, const uint16_t* d_depth,
         o_idx[k] = pk.add(N * P * 4);
     }
     int e;
-    if ((e = grow(&c->cloud_dev, &c->cloud_cap, pk.off, "dense_clouds"))) return e;
+    if ((e = c->cloud_dev.reserve(pk.off, 0, "dense_clouds"))) return e;
     if ((e = stage_reserve(c, host_bytes))) return e;
-    uint8_t *h = c->stage_h, *d = c->cloud_dev;
+    uint8_t *h = c->stage.p, *d = c->cloud_dev.p;
     if (Twc) {
         memcpy(h + o_twc, Twc, N * 64);
         HIPCHK(hipMemcpyAsync(d + o_twc, h + o_twc, N * 64, hipMemcpyHostToDevice, st));
@@ -96,10 +74,14 @@ static int run_clouds(odo_ctx* c, const uint8_t* d_bgr, const uint16_t* d_depth,
         max_points = std::max(max_points, np[f]);
     }
     // the points, then their counts
-    const size_t total = (size_t)off[N], cnt_at = (total * sizeof(odo_cloud_point) + 255) & ~(size_t)255;
-    if ((e = grow(&c->cloud_out, &c->cloud_out_cap, std::max(cnt_at + total * 4, (size_t)256), "dense_clouds"))) return e;
-    a.out = (odo_cloud_point*)c->cloud_out;
-    a.counts = (int32_t*)(c->cloud_out + cnt_at);
+    const size_t total = (size_t)off[N];
+    Pack po;
+    po.add(total * sizeof(odo_cloud_point));
+    const size_t cnt_at = po.off;
+    // never empty: a call without a point still hands out a device address
+    if ((e = c->cloud_out.reserve(std::max(cnt_at + total * 4, (size_t)256), 0, "dense_clouds"))) return e;
+    a.out = (odo_cloud_point*)c->cloud_out.p;
+    a.counts = (int32_t*)(c->cloud_out.p + cnt_at);
     launch_cloud_points(st, a, max_points);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(st));
@@ -151,10 +133,10 @@ int odo_get_dense_cloud(odo_ctx* c, int i, odo_cloud_point* pts, int32_t* counts
     const int np = c->cloud_np[i], m = std::min(np, cap);
     const size_t o = (size_t)c->cloud_off[i];
     if (m > 0) {
-        HIPCHK(hipMemcpy(pts, (const odo_cloud_point*)c->cloud_out + o, (size_t)m * sizeof(odo_cloud_point),
+        HIPCHK(hipMemcpy(pts, (const odo_cloud_point*)c->cloud_out.p + o, (size_t)m * sizeof(odo_cloud_point),
                          hipMemcpyDeviceToHost));
         if (counts)
-            HIPCHK(hipMemcpy(counts, (const int32_t*)(c->cloud_out + c->cloud_counts_at) + o, (size_t)m * 4,
+            HIPCHK(hipMemcpy(counts, (const int32_t*)(c->cloud_out.p + c->cloud_counts_at) + o, (size_t)m * 4,
                              hipMemcpyDeviceToHost));
     }
     *n = np;
@@ -167,8 +149,8 @@ int odo_dense_cloud_device(odo_ctx* c, int i, const odo_cloud_point** d_pts, con
     if ((e = cloud_at(c, i, "dense_cloud_device"))) return e;
     if (!d_pts || !n) return fail(ODO_ERR_ARG, "bad dense_cloud_device args");
     const size_t o = (size_t)c->cloud_off[i];
-    *d_pts = (const odo_cloud_point*)c->cloud_out + o;
-    if (d_counts) *d_counts = (const int32_t*)(c->cloud_out + c->cloud_counts_at) + o;
+    *d_pts = (const odo_cloud_point*)c->cloud_out.p + o;
+    if (d_counts) *d_counts = (const int32_t*)(c->cloud_out.p + c->cloud_counts_at) + o;
     *n = c->cloud_np[i];
     return ODO_OK;
 }

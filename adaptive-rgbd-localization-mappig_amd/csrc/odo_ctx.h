@@ -131,7 +131,43 @@ struct DevPool {
     }
 };
 
+// A grow-only block, device (hipMalloc) or page-locked (hipHostMalloc): one
+// allocation that reserve() replaces by a larger one when a call needs more
+// and that lives until release() or its owner's end. When it grows its
+// contents are lost. The capacity policy is the caller's: reserve() allocates
+// max(bytes, floor). A failed allocation leaves the block empty and HIP's last
+// error cleared, so that no later call reports it.
+template <bool PINNED>
+struct GrowBlock {
+    uint8_t* p = nullptr;
+    size_t cap = 0;
+    GrowBlock() = default;
+    GrowBlock(const GrowBlock&) = delete;
+    GrowBlock& operator=(const GrowBlock&) = delete;
+    ~GrowBlock() { release(); }
+    void release() {
+        if (p) (void)(PINNED ? hipHostFree(p) : hipFree(p));
+        p = nullptr;
+        cap = 0;
+    }
+    int reserve(size_t bytes, size_t floor, const char* who) {
+        if (bytes <= cap) return ODO_OK;
+        release();
+        const size_t want = std::max(bytes, floor);
+        if ((PINNED ? hipHostMalloc((void**)&p, want, hipHostMallocDefault) : hipMalloc((void**)&p, want)) != hipSuccess) {
+            p = nullptr;
+            (void)hipGetLastError();
+            return fail(ODO_ERR_DEVICE, std::string(who) + (PINNED ? ": hipHostMalloc failed" : ": hipMalloc failed"));
+        }
+        cap = want;
+        return ODO_OK;
+    }
+};
+using DevBlock = GrowBlock<false>;
+using PinnedBlock = GrowBlock<true>;
+
 struct HypSession;  // hypotheses-mode RANSAC state (odo_hyps.cpp)
+void free_hyp_session(HypSession* h);
 
 }  // namespace odo
 
@@ -214,15 +250,13 @@ struct odo_ctx {
     // page-locked staging of the per-stage (synchronous) entry points: their
     // inputs are packed here and uploaded with one DMA, their outputs come
     // back here with async copies into pinned memory and one sync
-    uint8_t* stage_h = nullptr;
-    size_t stage_cap = 0;
+    PinnedBlock stage;
     // hypotheses mode (odo_ransac_hyps*): device scratch kept across sessions
     // (grow-only: a session per pair used to hipMalloc / hipFree its own,
     // 0.5 ms of the 1.2 ms per pair of round 4) and the session's packed
     // inputs in page-locked memory (one DMA), reused once hyp_up has passed
     DevArena hyp_arena;
-    uint8_t* hyp_stage_h = nullptr;
-    size_t hyp_stage_cap = 0;
+    PinnedBlock hyp_stage;
     hipEvent_t hyp_up = nullptr;
     bool hyp_up_rec = false;
     int in_next = 0;
@@ -259,7 +293,8 @@ struct odo_ctx {
     // view_mode: the mode the last tracked batch ran in (-1: none / extraction only)
     int odo_mode = ODO_ODOMETRY_ADAPTIVE_RBA, view_mode = -1;
     odo_ricp_params ricp{};
-    // ADAPTIVE_RICP scratch (allocated by the first switch to the mode): one
+    // ADAPTIVE_RICP scratch (allocated by the first switch to the mode, all or
+    // nothing: rb[0].pool holds buffers exactly when it exists): one
     // copy per pair stream, batch b uses copy b & 1 on pair stream b & 1. The
     // batches of one stream run in order, so a copy is never shared by two
     // batches in flight and needs no event; odo_get_ricp reads view_rb, the
@@ -271,7 +306,6 @@ struct odo_ctx {
         odo_ricp_result* rec = nullptr;
         DevPool pool;
     } rb[2];
-    bool ricp_alloc = false;
     int view_rb = 0;
     // Batched TrackLocalMap scratch (odo_track_local_map), allocated by its
     // first call: the per-frame arrays for max_batch frames, the per-landmark
@@ -292,31 +326,23 @@ struct odo_ctx {
         odo_local_map_result* res = nullptr;
         DevPool pool;
     } lm;
-    bool lm_alloc = false;
-    int lm_cap = 0, lm_n = -1;
+    int lm_cap = 0, lm_n = -1;  // lm_cap 0: not allocated
     LmGrid lm_grid{};
-    // odo_local_ba's device block (upload, download and kernel scratch),
-    // allocated by its first call and regrown when a call needs more
-    uint8_t* ba_dev = nullptr;
-    size_t ba_cap = 0;
-    // odo_fuse_search's device block (upload, records, sorted points and cell
-    // starts), allocated by its first call and regrown when a call needs more
-    uint8_t* fuse_dev = nullptr;
-    size_t fuse_cap = 0;
+    // odo_local_ba's device block (upload, download and kernel scratch)
+    DevBlock ba_dev;
+    // odo_fuse_search's device block (upload, records, sorted points and cell starts)
+    DevBlock fuse_dev;
     // odo_dense_clouds: the scratch block (plans, histograms, the (key, pixel)
     // ping-pong of every frame of a call) and the output block (the points,
-    // then their counts at cloud_counts_at), each allocated by the first call
-    // and regrown when a call needs more. cloud_n: the frames of the last call
+    // then their counts at cloud_counts_at). cloud_n: the frames of the last call
     // (-1: none), cloud_off / cloud_np their first point and point count
-    uint8_t *cloud_dev = nullptr, *cloud_out = nullptr;
-    size_t cloud_cap = 0, cloud_out_cap = 0, cloud_counts_at = 0;
+    DevBlock cloud_dev, cloud_out;
+    size_t cloud_counts_at = 0;
     int cloud_n = -1;
     std::vector<int32_t> cloud_off, cloud_np;
     // the grid GICP entry points (odo_gicp_grid_batch, odo_gicp_grid_covariances,
-    // odo_gicp_dense): the point-sized block and the cell-sized block, each
-    // allocated by the first call and regrown when a call needs more
-    uint8_t *gg_pts = nullptr, *gg_cells = nullptr;
-    size_t gg_pts_cap = 0, gg_cells_cap = 0;
+    // odo_gicp_dense): the point-sized block and the cell-sized block
+    DevBlock gg_pts, gg_cells;
     // sequence state: the last tracked batch sits in frame set seq_set (its
     // last frame at slot seq_n); getters read view_set / view_n
     bool has_prev = false;
@@ -391,6 +417,28 @@ struct odo_ctx {
     // kt_ref, an event recorded when mode 2 was set
     hipEvent_t kt_ref = nullptr;
     std::vector<double> kt_marks;
+
+    // Frees exactly what exists (also a context whose creation failed
+    // half-way). Every owner above frees itself; the body releases them by hand
+    // only for the order, since members are destroyed after the body: device
+    // memory goes while the streams whose work may still use it exist (hipFree
+    // waits for that work), then the events, then the streams. An owner
+    // missing here is still freed, by its own destructor, after the streams.
+    ~odo_ctx() {
+        lm.pool.release();
+        for (DevBlock* b : {&ba_dev, &fuse_dev, &cloud_dev, &cloud_out, &gg_pts, &gg_cells}) b->release();
+        free_hyp_session(hs);
+        pool.release();
+        for (auto& R : rb) R.pool.release();
+        arena.release();
+        hyp_arena.release();
+        for (hipEvent_t e : events) (void)hipEventDestroy(e);
+        stage.release();
+        hyp_stage.release();
+        for (hipStream_t st : owned) (void)hipStreamDestroy(st);
+        if (h_open) (void)hipHostFree(h_open);
+        if (latch_set_h) (void)hipHostFree(latch_set_h);
+    }
 };
 
 namespace odo {
@@ -419,15 +467,6 @@ inline void tmark(odo_ctx* c, int i, hipStream_t st) {
     if (c->timing) (void)hipEventRecord(c->ev[i], st);
 }
 
-// Packed layout in the staging buffer: 256-byte aligned sections
-struct Pack {
-    size_t off = 0;
-    size_t add(size_t bytes) {
-        const size_t o = off;
-        off = (off + bytes + 255) & ~(size_t)255;
-        return o;
-    }
-};
 // a carve of the calling entry point's arena (no free: the arena owns it)
 struct DevBuf {
     void* p = nullptr;
@@ -441,7 +480,7 @@ struct DevBuf {
     if ((a).failed) return fail(ODO_ERR_DEVICE, "device scratch allocation failed")
 
 int sync_all(odo_ctx* c);                      // odo_capi.cpp
-int stage_reserve(odo_ctx* c, size_t bytes);   // grows c->stage_h (its contents are lost)
+int stage_reserve(odo_ctx* c, size_t bytes);   // grows c->stage (its contents are lost)
 int kt_collect(odo_ctx* c, int i);
 int build_geometry(odo_ctx* c);                // odo_geometry.cpp
 int reset_adaptive(odo_ctx* c);
@@ -450,10 +489,6 @@ int run_extract(odo_ctx* c, int set, const uint8_t* d_bgr, const uint16_t* d_dep
 void launch_set_knn2(odo_ctx* c, hipStream_t st, int s, int n);
 int run_knn(odo_ctx* c, hipStream_t st, int s, int n);  // k_vo_lm + launch_set_knn2
 int run_pair_match(odo_ctx* c, hipStream_t st, int set, int n, bool first_valid, bool latched);
-void free_local_map(odo_ctx* c);               // odo_stages.cpp
-void free_dense_clouds(odo_ctx* c);            // odo_cloud.cpp
-void free_gicp_grid(odo_ctx* c);               // odo_gicp_grid.cpp
-void free_hyp_session(HypSession* h);          // odo_hyps.cpp
 
 // One packed round trip of a synchronous entry point. The sections are laid
 // out with add(), the inputs first; the host side is the context's pinned
@@ -469,7 +504,7 @@ struct Staged {
     // the caller's own device block (at least pk.off bytes) ...
     int reserve(odo_ctx* c, uint8_t* block) {
         const int e = stage_reserve(c, pk.off);
-        h = c->stage_h;
+        h = c->stage.p;
         d = block;
         return e;
     }

@@ -9,28 +9,7 @@
 
 namespace odo {
 
-void free_gicp_grid(odo_ctx* c) {
-    if (c->gg_pts) (void)hipFree(c->gg_pts);
-    if (c->gg_cells) (void)hipFree(c->gg_cells);
-    c->gg_pts = c->gg_cells = nullptr;
-    c->gg_pts_cap = c->gg_cells_cap = 0;
-}
-
 namespace {
-
-// grow-only device block (its contents are lost when it grows)
-int grow(uint8_t** p, size_t* cap, size_t bytes) {
-    if (bytes <= *cap) return ODO_OK;
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-    *cap = 0;
-    if (hipMalloc((void**)p, bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(ODO_ERR_DEVICE, "gicp_grid: hipMalloc failed");
-    }
-    *cap = bytes;
-    return ODO_OK;
-}
 
 // the ICP rings of a grid of cell width w: the first r whose bound reaches
 // max_corr_dist^2 (every point beyond ring r is then too far to correspond)
@@ -147,8 +126,8 @@ int run(odo_ctx* c, const Source& src, const std::vector<int32_t>& offs, std::ve
                  o_outp = pk.add(W * 12), o_Mah = pk.add(W * 72), o_is = pk.add(W * 4), o_it = pk.add(W * 4),
                  o_T = pk.add(NP * 64), o_io = pk.add(NP * 16);
     int e;
-    if ((e = grow(&c->gg_pts, &c->gg_pts_cap, std::max(pk.off, (size_t)256)))) return e;
-    uint8_t* d = c->gg_pts;
+    if ((e = c->gg_pts.reserve(pk.off, 256, "gicp_grid"))) return e;
+    uint8_t* d = c->gg_pts.p;
     hipStream_t st = c->stream;
     float* dP = (float*)(d + o_P);
     int* doffs = (int*)(d + o_offs);
@@ -195,8 +174,8 @@ int run(odo_ctx* c, const Source& src, const std::vector<int32_t>& offs, std::ve
     const size_t M = (size_t)total + 1, NB = (M + 4095) / 4096;
     Pack pc;
     const size_t o_cnt = pc.add(M * 4), o_fill = pc.add(M * 4), o_bsum = pc.add(NB * 4);
-    if ((e = grow(&c->gg_cells, &c->gg_cells_cap, pc.off))) return e;
-    uint8_t* dc = c->gg_cells;
+    if ((e = c->gg_cells.reserve(pc.off, 0, "gicp_grid"))) return e;
+    uint8_t* dc = c->gg_cells.p;
     HIPCHK(hipMemsetAsync(dc, 0, o_bsum, st));  // cnt and fill
     if (ncl) HIPCHK(hipMemcpyAsync(d + o_cl, cl.data(), NC * sizeof(GgCloud), hipMemcpyHostToDevice, st));
     const GgCloud* dcl = (const GgCloud*)(d + o_cl);
@@ -345,7 +324,7 @@ int odo_gicp_dense(odo_ctx* c, const int32_t* pairs, int nprob, const float* gue
     std::vector<int32_t> offs(1, 0);
     std::vector<GgPair> pr((size_t)nprob);
     Source s;
-    s.dev = (const float*)c->cloud_out;
+    s.dev = (const float*)c->cloud_out.p;
     s.stride = (int)(sizeof(odo_cloud_point) / 4);
     for (int k = 0; k < 2 * nprob; k++) {
         const int f = pairs[k];

@@ -165,23 +165,15 @@ static int hyps_launch(odo_ctx* c, const odo_dmatch* m12, int n12, const float* 
     // The previous session's upload must have left the buffer before it is
     // refilled.
     if (c->hyp_up_rec) HIPCHK(hipEventSynchronize(c->hyp_up));
-    if (up > c->hyp_stage_cap) {
-        if (c->hyp_stage_h) (void)hipHostFree(c->hyp_stage_h);
-        c->hyp_stage_h = nullptr;
-        c->hyp_stage_cap = 0;
-        const size_t cap = std::max(up, (size_t)1 << 20);
-        if (hipHostMalloc((void**)&c->hyp_stage_h, cap, hipHostMallocDefault) != hipSuccess)
-            return fail(ODO_ERR_DEVICE, "hipHostMalloc (hypotheses staging) failed");
-        c->hyp_stage_cap = cap;
-    }
+    if (const int e = c->hyp_stage.reserve(up, (size_t)1 << 20, "hypotheses staging")) return e;
     if (!c->hyp_up) {
         const hipError_t ee = c->make_event(&c->hyp_up, SYNC_EVENT_FLAGS);
         if (ee != hipSuccess)
             return fail(ODO_ERR_DEVICE, std::string("hipEventCreateWithFlags(&c->hyp_up, SYNC_EVENT_FLAGS): ") +
                                             hipGetErrorString(ee));
     }
-    fill_pair(c->hyp_stage_h, S.o, in, xyz1, xyz2, latch, rng);
-    HIPCHK(hipMemcpyAsync(S.d, c->hyp_stage_h, up, hipMemcpyHostToDevice, st));
+    fill_pair(c->hyp_stage.p, S.o, in, xyz1, xyz2, latch, rng);
+    HIPCHK(hipMemcpyAsync(S.d, c->hyp_stage.p, up, hipMemcpyHostToDevice, st));
     HIPCHK(hipEventRecord(c->hyp_up, st));
     c->hyp_up_rec = true;
     int* ints = S.at<int>(S.o.ints);

@@ -25,7 +25,18 @@ static inline const char* odo_knob(const char* name) {
 #endif
 }
 
-#define FAST_ROI_MAX 72  // largest FAST cell ROI side (a level narrower than 2 cells: up to 65)
+// The one carver: a block cut into 256-byte aligned sections. add() returns
+// the section's offset; off is then the size of the block so far.
+struct Pack {
+    size_t off = 0;
+    size_t add(size_t bytes) {
+        const size_t o = off;
+        off = (off + bytes + 255) & ~(size_t)255;
+        return o;
+    }
+};
+
+#define FAST_ROI_MAX 72 // largest FAST cell ROI side (a level narrower than 2 cells: up to 65)
 
 // One pyramid level of one frame (all frames share the geometry).
 struct LevelDesc {

@@ -7,9 +7,8 @@
 #include "odo_ctx.h"
 
 // Batched TrackLocalMap scratch: max_batch frames, lm_cap landmarks
-void odo::free_local_map(odo_ctx* c) {
+static void free_local_map(odo_ctx* c) {
     c->lm.pool.release();
-    c->lm_alloc = false;
     c->lm_cap = 0;
     c->lm_n = -1;
 }
@@ -40,7 +39,6 @@ static int alloc_local_map(odo_ctx* c, int lm_cap) {
     std::fill(ints.begin() + B, ints.end(), 1 << 30);
     HIPCHK(hipMemcpy(L.ints, ints.data(), ints.size() * sizeof(int), hipMemcpyHostToDevice));
     c->lm_cap = lm_cap;
-    c->lm_alloc = true;
     return ODO_OK;
 }
 
@@ -599,15 +597,7 @@ int odo_fuse_search(odo_ctx* c, const odo_fuse_kf* kfs, int n_kf, const float* k
     // on the device the sorted points and the cell starts follow the pack
     Pack scr = s.pk;
     const size_t o_bpt = scr.add((size_t)kp_off[NK] * sizeof(float4)), o_cs = scr.add(NK * (ncells + 1) * 4);
-    if (scr.off > c->fuse_cap) {
-        if (c->fuse_dev) (void)hipFree(c->fuse_dev);
-        c->fuse_dev = nullptr;
-        c->fuse_cap = 0;
-        const size_t cap = std::max(scr.off, (size_t)1 << 20);
-        if (hipMalloc((void**)&c->fuse_dev, cap) != hipSuccess) return fail(ODO_ERR_DEVICE, "fuse_search: hipMalloc failed");
-        c->fuse_cap = cap;
-    }
-    if ((e = s.reserve(c, c->fuse_dev))) return e;
+    if ((e = c->fuse_dev.reserve(scr.off, (size_t)1 << 20, "fuse_search")) || (e = s.reserve(c, c->fuse_dev.p))) return e;
     memcpy(s.host<odo_fuse_kf>(o_kf), kfs, NK * sizeof(odo_fuse_kf));
     memcpy(s.host<int32_t>(o_ko), kp_off.data(), (NK + 1) * 4);
     memcpy(s.host<int32_t>(o_ro), rec_off.data(), (NK + 1) * 4);
@@ -661,7 +651,7 @@ int odo_track_local_map(odo_ctx* c, const odo_landmark* lms, int nL, const float
     int e;
     if ((e = sync_all(c))) return e;
     c->lm_n = -1;
-    if (!c->lm_alloc || nL > c->lm_cap) {
+    if (c->lm_cap == 0 || nL > c->lm_cap) {
         free_local_map(c);
         if ((e = alloc_local_map(c, std::max((nL + 1023) & ~1023, 4096)))) {  // all or nothing
             free_local_map(c);
@@ -834,15 +824,7 @@ int odo_local_ba(odo_ctx* c, float* Tcw, const uint8_t* kf_fixed, int n_kf, floa
     // the per-trial scalars do (reserved first: growing loses the contents)
     const size_t io_bytes = s.pk.off, need = io_bytes + ba_scratch_bytes(n_kf, n_lm, n_edges, nf);
     if ((e0 = stage_reserve(c, io_bytes + 256))) return e0;
-    if (need > c->ba_cap) {
-        if (c->ba_dev) (void)hipFree(c->ba_dev);
-        c->ba_dev = nullptr;
-        c->ba_cap = 0;
-        const size_t cap = std::max(need, (size_t)1 << 20);
-        if (hipMalloc((void**)&c->ba_dev, cap) != hipSuccess) return fail(ODO_ERR_DEVICE, "local_ba: hipMalloc failed");
-        c->ba_cap = cap;
-    }
-    if ((e0 = s.reserve(c, c->ba_dev))) return e0;
+    if ((e0 = c->ba_dev.reserve(need, (size_t)1 << 20, "local_ba")) || (e0 = s.reserve(c, c->ba_dev.p))) return e0;
     memcpy(s.host<float>(o_T), Tcw, NK * 64);
     memcpy(s.host<float>(o_X), Xw, NL * 12);
     memcpy(s.host<int32_t>(o_pidx), pidx.data(), NK * 4);

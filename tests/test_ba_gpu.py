@@ -160,6 +160,38 @@ def test_repeatable_and_scratch_growth(ctx):
         odo.close()
 
 
+def test_block_regrows_past_its_floor_and_results_repeat(ctx):
+    """A fresh context: a small call, one that outgrows the device block, the
+    small one again. The block starts at its floor of 1 MiB and holds the packed
+    inputs and outputs plus ba_scratch_bytes. The large problem is 4 free and 1
+    fixed keyframe that each see all 2048 landmarks: 5 * 2048 = 10 240 edges.
+    The per-edge scratch sections alone (c2 8, W 144, flags 1, flist 8 = 161
+    bytes an edge) take 10 240 * 161 = 1 648 640 bytes > 1 048 576. The small
+    results are byte-identical, and the large one equals the same call on
+    another fresh context."""
+    pkg = pkg_of(ctx)
+    small = B.ba_case("s2_1_16")
+    big = B.make_scene([0xB16, 0], 4, 1, 2048, obs="all", iters_robust=2, iters_final=2)
+    assert len(big["edges"]) == 10240
+
+    def fresh():
+        return pkg, pkg.Odometry(pkg.default_config(640, 480, 1, nfeatures=500, iterations=50))
+
+    def as_bytes(r):
+        return r[0].tobytes(), r[1].tobytes(), r[2].tobytes(), bytes(r[3])
+
+    one, two = fresh(), fresh()
+    try:
+        a = as_bytes(run(one, small))
+        b = as_bytes(run(one, big))
+        assert as_bytes(run(one, small)) == a
+        assert as_bytes(run(two, big)) == b
+        assert run(two, big)[3].status == pkg.BA_RAN
+    finally:
+        one[1].close()
+        two[1].close()
+
+
 def test_nothing_to_do(ctx):
     pkg, odo = ctx
     c = B.ba_case("s2_1_16")

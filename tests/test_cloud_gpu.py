@@ -238,6 +238,29 @@ def test_argument_errors_write_nothing(ctx):
         fresh.close()
 
 
+def test_blocks_regrow_and_results_repeat():
+    """A fresh context: one frame, then two (both blocks are sized exactly, so
+    the scratch block and the output block regrow), then the one frame again.
+    The one-frame results are byte-identical, frame 0 is still readable after
+    the last call, and the two-frame result equals the same call on another
+    fresh context."""
+    pkg = load_pkg()
+    bgr, dep, _ = sequence(2)
+    bgr, dep = np.ascontiguousarray(bgr), np.ascontiguousarray(dep)
+    one, two = (pkg.Odometry(pkg.default_config(R.W, R.H, 2, nfeatures=500, iterations=50)) for _ in range(2))
+    try:
+        a = run(one, bgr[:1], dep[:1], 0.03)
+        b = run(one, bgr, dep, 0.03)
+        assert b[0]["n_points"].sum() > a[0]["n_points"].sum() > 0
+        again = run(one, bgr[:1], dep[:1], 0.03)
+        assert same(a, again) and len(again[1]) == 1
+        assert one.get_dense_cloud(0, counts=True)[0].tobytes() == a[1][0][0].tobytes()
+        assert same(b, run(two, bgr, dep, 0.03)) and len(b[1]) == 2
+    finally:
+        one.close()
+        two.close()
+
+
 def test_tracking_is_undisturbed(ctx):
     """The pair records of two tracked batches are the same with a dense-cloud
     call between them (and one before and after) as without."""

@@ -172,6 +172,37 @@ def test_above_the_brute_force_capacity(odo):
     np.testing.assert_allclose(Tg, ref["T"], rtol=0, atol=1e-5)
 
 
+def test_blocks_regrow_and_results_repeat():
+    """A fresh context: a pair of 20-point clouds, a pair of 300-point clouds
+    three times as wide, the 20-point pair again, all at one forced cell of
+    0.25. The point-sized block is sized by the points of a call (40, then 600),
+    the cell-sized block by its cells: the wide clouds hold the small ones'
+    points scaled by 3, so no axis of theirs has fewer cells and the table is
+    larger. Both blocks regrow. The small results are identical, and the large
+    one equals the same call on another fresh context."""
+    pkg = load_pkg()
+    small = (*G.icp_pair(20, 20), None)
+    wide = np.ascontiguousarray(G.scene(300) * np.float32(3))
+    large = (wide, G.shifted(wide), None)
+    ext = lambda P: P.max(0) - P.min(0)
+    assert np.all(np.floor(ext(wide) / 0.25) > np.floor(ext(small[0]) / 0.25))
+
+    def call(o, pair):
+        T, conv, it, nc = o.gicp_grid_batch([pair], 10, 0.07, 0.25)[0]
+        return T.tobytes(), conv, it, nc
+
+    one, two = (pkg.Odometry(pkg.default_config(640, 480, 1)) for _ in range(2))
+    try:
+        a = call(one, small)
+        b = call(one, large)
+        assert call(one, small) == a
+        assert call(two, large) == b
+        assert a[1] == 1 and b[3] > 0
+    finally:
+        one.close()
+        two.close()
+
+
 # ================================================================= arguments
 def test_far_cloud_and_the_table_budget(odo):
     P = R.cloud("far")

@@ -80,6 +80,59 @@ def test_virtual_ranks_reproduce_iterate(world, corrupt, iters):
         odo.close()
 
 
+def _session(pkg, odo, m, x1, x2, iters, seed):
+    """One hypotheses-mode session over all of [0, iters) on one context:
+    the summaries, the fold, the finish. Everything it returns, as bytes."""
+    from arlm_amd import hyp_shard
+    lib = pkg.load()
+    params = pkg.RansacParams(iters, 20, 3.0, 4, 1)
+    rng = pkg.Rng()
+    lib.odo_rng_seed(pkg.ptr(rng), seed)
+    lat, ng = O.C.c_double(float("nan")), O.C.c_int(0)
+    hyps = np.zeros(iters, pkg._abi.HYP_DTYPE)
+    pkg.check(lib.odo_ransac_hyps(odo.h, pkg.ptr(m), m.size, pkg.ptr(x1), x1.shape[0], pkg.ptr(x2), x2.shape[0],
+                                  pkg.ptr(params), pkg.ptr(rng), O.C.byref(lat), 0, iters, pkg.ptr(hyps), O.C.byref(ng)))
+    fr = hyp_shard.fold(hyps, ng.value, params)
+    T = np.zeros(16, np.float32)
+    rmse, ni, ok, own = O.C.c_float(0), O.C.c_int(0), O.C.c_int(0), O.C.c_int(0)
+    inl = np.zeros(max(m.size, 1), pkg.DMATCH_DTYPE)
+    pkg.check(lib.odo_ransac_hyps_finish(odo.h, pkg.ptr(fr), pkg.ptr(rng), pkg.ptr(T), O.C.byref(rmse), pkg.ptr(inl),
+                                         O.C.byref(ni), O.C.byref(ok), O.C.byref(own)))
+    assert own.value == 1
+    return (hyps.tobytes(), ng.value, lat.value, T.tobytes(), rmse.value, inl[:ni.value].tobytes(), ok.value, bytes(rng))
+
+
+def test_sessions_alternate_between_a_small_and_a_large_pair():
+    """A fresh context: a session over a small pair, one over a larger pair,
+    the small one again. The larger pair regrows the device arena's block and
+    the page-locked block of the packed upload, whose floor is 1 MiB: the
+    entry point sets no limit on the frames' point counts, so its frames carry
+    46 000 points each (the pair's own, then filler that no match names), and
+    the xyz section alone is 2 * 46 000 * 12 = 1 104 000 bytes > 1 048 576. Its
+    matches are the small pair's with every second trainIdx moved on by one
+    place. The small sessions are byte-identical, and the large one equals the
+    same session on another fresh context."""
+    pkg = load_pkg()
+    iters = 500
+    m, x1, x2, _ = _problem(0.0, iters)
+    x1, x2 = np.ascontiguousarray(x1), np.ascontiguousarray(x2)
+    mb = m.copy()
+    mb["trainIdx"][::2] = np.roll(m["trainIdx"][::2], 1)
+    fill = np.random.default_rng(3).uniform(0.5, 4.0, (46000, 3)).astype(np.float32)
+    b1, b2 = fill.copy(), fill.copy()
+    b1[:len(x1)], b2[:len(x2)] = x1, x2
+    one, two = (pkg.Odometry(pkg.default_config(640, 480, 1, nfeatures=1000, iterations=iters)) for _ in range(2))
+    try:
+        a = _session(pkg, one, m, x1, x2, iters, 99)
+        b = _session(pkg, one, mb, b1, b2, iters, 99)
+        assert _session(pkg, one, m, x1, x2, iters, 99) == a
+        assert _session(pkg, two, mb, b1, b2, iters, 99) == b
+        assert a[6] == 1 and b[0] != a[0]
+    finally:
+        one.close()
+        two.close()
+
+
 def _free_port():
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))

@@ -20,7 +20,8 @@ from ._abi import (DETECTOR_ADAPTIVE_FAST, DETECTOR_ADAPTIVE_ORB, DETECTOR_ORB_S
                    ODOMETRY_ADAPTIVE_RBA, ODOMETRY_ADAPTIVE_RICP, ODOMETRY_RANSAC, RicpParams, RicpResult,
                    BA_EDGE_DTYPE, BA_NOTHING, BA_RAN, BaParams, BaResult,
                    FUSE_BAD, FUSE_BEHIND, FUSE_CAND_DTYPE, FUSE_CANDS, FUSE_KF_DTYPE, FUSE_NULL, FUSE_OUTSIDE,
-                   CLOUD_DTYPE, CLOUD_INFO_DTYPE, CLOUD_OK, CLOUD_UNFILTERED, ERR_CAPACITY)
+                   CLOUD_DTYPE, CLOUD_INFO_DTYPE, CLOUD_OK, CLOUD_UNFILTERED, ERR_CAPACITY, SOR_INFO_DTYPE,
+                   SOR_OK, SOR_SKIPPED, SOR_MAX_K)
 
 __all__ = ["Odometry", "HostFrames", "PinnedResults", "default_config", "load", "KP_DTYPE", "DMATCH_DTYPE", "PAIR_DTYPE", "rng_stream",
            "kabsch", "Calib", "OrbParams", "RansacParams", "Config", "AdaptiveParams", "DETECTOR_ORB_SLAM2",
@@ -30,7 +31,8 @@ __all__ = ["Odometry", "HostFrames", "PinnedResults", "default_config", "load", 
            "RicpParams", "RicpResult", "default_ricp_params", "LANDMARK_DTYPE", "LOCAL_MAP_DTYPE", "LocalMapResult",
            "LM_BAD", "LM_SEEN", "LM_HAS_OBS", "BA_EDGE_DTYPE", "BaParams", "BaResult", "BA_RAN", "BA_NOTHING",
            "default_ba_params", "fuse_best", "FUSE_KF_DTYPE", "FUSE_CAND_DTYPE", "FUSE_CANDS", "FUSE_NULL", "FUSE_BAD",
-           "FUSE_BEHIND", "FUSE_OUTSIDE", "CLOUD_DTYPE", "CLOUD_INFO_DTYPE", "CLOUD_OK", "CLOUD_UNFILTERED"]
+           "FUSE_BEHIND", "FUSE_OUTSIDE", "CLOUD_DTYPE", "CLOUD_INFO_DTYPE", "CLOUD_OK", "CLOUD_UNFILTERED",
+           "SOR_INFO_DTYPE", "SOR_OK", "SOR_SKIPPED", "SOR_MAX_K"]
 
 
 def default_config(width=640, height=480, max_batch=1, nfeatures=1000, iterations=200, seed=0x5EED0000,
@@ -728,6 +730,65 @@ class Odometry:
         check(self.lib.odo_gicp_dense(self.h, ptr(pr), P, None if g is None else ptr(g), max_iterations,
                                       max_corr_dist, ptr(T), ptr(conv), ptr(it), ptr(nc)))
         return [(T[p].reshape(4, 4), int(conv[p]), int(it[p]), int(nc[p])) for p in range(P)]
+
+    def dense_sor(self, mean_k: int = 50, stddev_mul: float = 1.0):
+        """odo_dense_sor: Frame::StatisticalOutlierRemovalFilterCloud(mean_k,
+        stddev_mul) on every cloud of the last dense-cloud call, in HBM. Returns
+        the SOR_INFO_DTYPE records, one per frame."""
+        info = np.zeros(self.cfg.max_batch, SOR_INFO_DTYPE)  # a dense-cloud call has at most max_batch frames
+        info["status"] = -1
+        check(self.lib.odo_dense_sor(self.h, mean_k, stddev_mul, ptr(info)))
+        return info[info["status"] >= 0].copy()
+
+    def cloud_sor_batch(self, clouds, mean_k: int = 50, stddev_mul: float = 1.0, cell: float = 0.0):
+        """odo_cloud_sor_batch: StatisticalOutlierRemoval of a list of n x 3
+        clouds in one launch chain. Returns (keeps: list of bool arrays,
+        distances: list of float32 arrays, SOR_INFO_DTYPE records)."""
+        offs = np.zeros(len(clouds) + 1, np.int32)
+        offs[1:] = np.cumsum([len(c) for c in clouds])
+        P = np.ascontiguousarray(np.concatenate([np.asarray(c, np.float32).reshape(-1, 3) for c in clouds])
+                                 if clouds else np.zeros((0, 3), np.float32))
+        N = max(int(offs[-1]), 1)
+        keep, dist = np.zeros(N, np.uint8), np.full(N, np.nan, np.float32)
+        info = np.zeros(max(len(clouds), 1), SOR_INFO_DTYPE)
+        check(self.lib.odo_cloud_sor_batch(self.h, ptr(P), ptr(offs), len(clouds), mean_k, stddev_mul, cell, ptr(keep),
+                                           ptr(dist), ptr(info)))
+        cut = lambda a: [a[offs[k]:offs[k + 1]] for k in range(len(clouds))]
+        return cut(keep.astype(bool)), cut(dist), info[:len(clouds)]
+
+    def gicp_grid_fitness(self, pairs, cell: float = 0.0):
+        """odo_gicp_grid_fitness: getFitnessScore for a list of (src n x 3, tgt m x
+        3, T 4x4 or None). Returns (scores float64, list of per-source-point
+        nearest squared distances)."""
+        P = len(pairs)
+        so = np.zeros(P + 1, np.int32)
+        to = np.zeros(P + 1, np.int32)
+        so[1:] = np.cumsum([len(s) for s, _, _ in pairs])
+        to[1:] = np.cumsum([len(t) for _, t, _ in pairs])
+        cat = lambda xs: np.ascontiguousarray(np.concatenate([np.asarray(x, np.float32).reshape(-1, 3) for x in xs])
+                                              if xs else np.zeros((0, 3), np.float32))
+        src, tgt = cat([s for s, _, _ in pairs]), cat([t for _, t, _ in pairs])
+        T = np.ascontiguousarray(np.stack([np.eye(4, dtype=np.float32) if q is None else np.asarray(q, np.float32)
+                                           for _, _, q in pairs]) if P else np.zeros((1, 4, 4), np.float32))
+        score = np.zeros(max(P, 1))
+        nn = np.full(max(int(so[-1]), 1), np.nan, np.float32)
+        check(self.lib.odo_gicp_grid_fitness(self.h, ptr(src), ptr(so), ptr(tgt), ptr(to), ptr(T), P, cell, ptr(score),
+                                             ptr(nn)))
+        return score[:P], [nn[so[p]:so[p + 1]] for p in range(P)]
+
+    def gicp_dense_fitness(self, pairs, T=None):
+        """odo_gicp_dense_fitness: getFitnessScore for a list of (source frame,
+        target frame) of the last dense-cloud call under T (a list of 4x4 or
+        None per pair, or None: identities). Returns the float64 scores."""
+        P = len(pairs)
+        pr = np.ascontiguousarray(np.asarray(pairs, np.int32).reshape(-1, 2) if P else np.zeros((1, 2), np.int32))
+        Ts = [None] * P if T is None else list(T)
+        assert len(Ts) == P
+        M = np.ascontiguousarray(np.stack([np.eye(4, dtype=np.float32) if q is None else np.asarray(q, np.float32)
+                                           for q in Ts]) if P else np.zeros((1, 4, 4), np.float32))
+        score = np.zeros(max(P, 1))
+        check(self.lib.odo_gicp_dense_fitness(self.h, ptr(pr), P, ptr(M), ptr(score)))
+        return score[:P]
 
     def timings(self):
         ms = np.zeros(16, np.float32)

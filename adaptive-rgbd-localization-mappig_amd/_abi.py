@@ -113,6 +113,8 @@ class PairStageOut(C.Structure):
 
 BA_RAN, BA_NOTHING = 0, 1  # include/odo_types.h ODO_BA_*
 CLOUD_OK, CLOUD_UNFILTERED = 0, 1  # include/odo_types.h ODO_CLOUD_*
+SOR_OK, SOR_SKIPPED = 0, 1  # include/odo_types.h ODO_SOR_*
+SOR_MAX_K = 64  # include/odo.h: mean_k above it is ODO_ERR_CAPACITY
 ODOMETRY_ADAPTIVE_RBA = 0   # include/odo.h ODO_ODOMETRY_ADAPTIVE_RBA
 ODOMETRY_RANSAC = 1         # include/odo.h ODO_ODOMETRY_RANSAC
 ODOMETRY_ADAPTIVE_RICP = 2  # include/odo.h ODO_ODOMETRY_ADAPTIVE_RICP
@@ -172,6 +174,8 @@ CLOUD_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("b", "u1"), (
                         ("a", "u1")])  # odo_cloud_point
 CLOUD_INFO_DTYPE = np.dtype([("status", "<i4"), ("n_valid", "<i4"), ("n_points", "<i4"), ("min_b", "<i4", 3),
                              ("div_b", "<i4", 3), ("min_p", "<f4", 3), ("max_p", "<f4", 3)])  # odo_cloud_info
+SOR_INFO_DTYPE = np.dtype([("status", "<i4"), ("n_in", "<i4"), ("n_out", "<i4"), ("pad", "<i4"), ("mean", "<f8"),
+                           ("stddev", "<f8"), ("threshold", "<f8")])  # odo_sor_info
 
 # Every symbol include/odo.h declares, with its ctypes signature.
 SIGNATURES = {
@@ -244,6 +248,10 @@ SIGNATURES = {
     "odo_dense_clouds_host": (C.c_int, [P, P, P, C.c_int, C.c_float, P, P]),
     "odo_get_dense_cloud": (C.c_int, [P, C.c_int, P, P, C.c_int, P]),
     "odo_dense_cloud_device": (C.c_int, [P, C.c_int, P, P, P]),
+    "odo_dense_sor": (C.c_int, [P, C.c_int, C.c_double, P]),
+    "odo_cloud_sor_batch": (C.c_int, [P, P, P, C.c_int, C.c_int, C.c_double, C.c_float, P, P, P]),
+    "odo_gicp_grid_fitness": (C.c_int, [P, P, P, P, P, P, C.c_int, C.c_float, P, P]),
+    "odo_gicp_dense_fitness": (C.c_int, [P, P, C.c_int, P, P]),
     "odo_default_ba_params": (None, [P]),
     "odo_local_ba": (C.c_int, [P, P, P, C.c_int, P, C.c_int, P, C.c_int, P, P, P, P]),
     "odo_ransac_hyps": (C.c_int, [P, P, C.c_int, P, C.c_int, P, C.c_int, P, P, P, C.c_int, C.c_int, P, P]),

@@ -25,6 +25,16 @@
 //                    of cells, stopped by gg_ring_bound; then cov_finish;
 //   k_gicp_grid      k_gicp's body with the correspondence search over the cells
 //                    within max_corr_dist of the query.
+// The ring walk exists once (gg_walk, a template over a visitor) and also serves
+// Frame::StatisticalOutlierRemovalFilterCloud (frame.cpp:228-238) and
+// GeneralizedICP::mScore = getFitnessScore() (generalizedicp.cpp:82), DESIGN §4
+// "SOR and fitness":
+//   k_sor_dist       the mean_k + 1 nearest distances of every point in a per-lane
+//                    LDS max-heap, PCL's distances[];
+//   k_sor_stats / _mark / _scan / _pack  mean, stddev and threshold per cloud in a
+//                    fixed order, the keep bytes, a stable compaction;
+//   k_gicp_fit_nn / _sum  the nearest target distance of every transformed source
+//                    point without a distance cap, and their mean per pair.
 // The restatement, its pinned choices and the oracle are in oracle/gicp_ref.cpp
 // (PCL is absent: parity with the library is unpinned).
 #include <hip/hip_runtime.h>
@@ -937,30 +947,19 @@ __global__ __launch_bounds__(256) void k_gg_scatter(const float* __restrict__ P,
     sorted[pos] = make_float4(P[3 * row], P[3 * row + 1], P[3 * row + 2], __int_as_float(i));
 }
 
-// grid (point blocks, clouds): one lane per point, in cell order, so that a
-// wave walks the same cells. The top 20 by (distance, index) over Chebyshev
-// rings around the point's cell, until the 20th distance held is below what
-// any unseen point can have (gg_ring_bound) or the rings have covered the grid.
-__global__ __launch_bounds__(64) void k_gicp_cov_grid(const float* __restrict__ P, const GgCloud* __restrict__ cl,
-                                                      const int* __restrict__ cstart,
-                                                      const float4* __restrict__ sorted, double* __restrict__ C,
-                                                      double eps) {
-    const GgCloud g = cl[blockIdx.y];
-    const int s = blockIdx.x * 64 + threadIdx.x;
-    if (g.n < 20 || s >= g.n) return;
-    const float4 me = sorted[(size_t)g.p0 + s];
-    const float pq[3] = {me.x, me.y, me.z};
-    int c[3];
-    gg_cell3(g, pq, c);
-    // as cov_point: +inf padding, whose index 0 no candidate goes below
-    float nd[GI_K];
-    int nn[GI_K];
-#pragma unroll
-    for (int j = 0; j < GI_K; j++) {
-        nd[j] = __builtin_inff();
-        nn[j] = 0;
-    }
-    const int* cs = cstart + g.c0;
+// The ring walk, once: every point of the cells at Chebyshev distance 0, 1, 2
+// ... from cell c goes to v.visit(row of `sorted`), and after ring r the walk
+// stops when the k-th distance the visitor holds (v.kth(), +inf while it holds
+// fewer) is STRICTLY below what any unseen point can have (gg_ring_bound), or
+// when the rings have covered the grid. c is gg_cell3 of the query. For a query
+// q outside the cloud's bounds that is also the cell of q', q clamped per axis
+// into the bounds (the computed t is monotone in the coordinate and the
+// bounds' own cells are 0 and dim - 1), and |p_a - q_a| >= |p_a - q'_a| for
+// every point p of the cloud and every axis a, so the bound that holds for q'
+// holds for any finite q (DESIGN §4 "SOR and fitness").
+template <class V>
+__device__ __forceinline__ void gg_walk(const GgCloud& g, const int* __restrict__ cs,
+                                        const float4* __restrict__ sorted, const int* c, V& v) {
     const int rmax = max(max(max(c[0], g.gx - 1 - c[0]), max(c[1], g.gy - 1 - c[1])), max(c[2], g.gz - 1 - c[2]));
     for (int r = 0;; r++) {
         const int z0 = max(c[2] - r, 0), z1 = min(c[2] + r, g.gz - 1);
@@ -981,31 +980,268 @@ __global__ __launch_bounds__(64) void k_gicp_cov_grid(const float* __restrict__ 
                         if (xa < 0 || xa > g.gx - 1) continue;
                     }
                     const int e = cs[row + xb + 1];
-                    for (int i = cs[row + xa]; i < e; i++) {
-                        const float4 t = sorted[i];
-                        const float pi[3] = {t.x, t.y, t.z};
-                        const int idx = __float_as_int(t.w);
-                        const float d = dist2f(pq, pi);
-#define GG_LT(j) (d < nd[j] || (d == nd[j] && idx < nn[j]))
-                        if (!GG_LT(GI_K - 1)) continue;
-#pragma unroll
-                        for (int j = GI_K - 1; j > 0; j--) {
-                            const bool up = GG_LT(j - 1);
-                            const bool here = !up && GG_LT(j);
-                            nd[j] = up ? nd[j - 1] : (here ? d : nd[j]);
-                            nn[j] = up ? nn[j - 1] : (here ? idx : nn[j]);
-                        }
-                        if (GG_LT(0)) {
-                            nd[0] = d;
-                            nn[0] = idx;
-                        }
-#undef GG_LT
-                    }
+                    for (int i = cs[row + xa]; i < e; i++) v.visit(sorted[i]);
                 }
             }
-        if (r >= rmax || (double)nd[GI_K - 1] < gg_ring_bound(g.w, g.slack, r)) break;
+        if (r >= rmax || (double)v.kth() < gg_ring_bound(g.w, g.slack, r)) break;
     }
-    cov_finish(P + 3 * (size_t)g.p0, nn, __float_as_int(me.w), eps, C + 9 * (size_t)g.p0);
+}
+
+// the covariance neighbours: the top 20 by (distance, index) in registers
+// (an unrolled insertion list; as cov_point: +inf padding, whose index 0 no
+// candidate goes below)
+struct CovTop20 {
+    float pq[3];
+    float nd[GI_K];
+    int nn[GI_K];
+    __device__ __forceinline__ void init() {
+#pragma unroll
+        for (int j = 0; j < GI_K; j++) {
+            nd[j] = __builtin_inff();
+            nn[j] = 0;
+        }
+    }
+    __device__ __forceinline__ void visit(const float4 t) {
+        const float pi[3] = {t.x, t.y, t.z};
+        const int idx = __float_as_int(t.w);
+        const float d = dist2f(pq, pi);
+#define GG_LT(j) (d < nd[j] || (d == nd[j] && idx < nn[j]))
+        if (!GG_LT(GI_K - 1)) return;
+#pragma unroll
+        for (int j = GI_K - 1; j > 0; j--) {
+            const bool up = GG_LT(j - 1);
+            const bool here = !up && GG_LT(j);
+            nd[j] = up ? nd[j - 1] : (here ? d : nd[j]);
+            nn[j] = up ? nn[j - 1] : (here ? idx : nn[j]);
+        }
+        if (GG_LT(0)) {
+            nd[0] = d;
+            nn[0] = idx;
+        }
+#undef GG_LT
+    }
+    __device__ __forceinline__ float kth() const { return nd[GI_K - 1]; }
+};
+
+// grid (point blocks, clouds): one lane per point, in cell order, so that a
+// wave walks the same cells. The top 20 by (distance, index) over the ring walk.
+__global__ __launch_bounds__(64) void k_gicp_cov_grid(const float* __restrict__ P, const GgCloud* __restrict__ cl,
+                                                      const int* __restrict__ cstart,
+                                                      const float4* __restrict__ sorted, double* __restrict__ C,
+                                                      double eps) {
+    const GgCloud g = cl[blockIdx.y];
+    const int s = blockIdx.x * 64 + threadIdx.x;
+    if (g.n < 20 || s >= g.n) return;
+    const float4 me = sorted[(size_t)g.p0 + s];
+    CovTop20 v;
+    v.pq[0] = me.x;
+    v.pq[1] = me.y;
+    v.pq[2] = me.z;
+    v.init();
+    int c[3];
+    gg_cell3(g, v.pq, c);
+    gg_walk(g, cstart + g.c0, sorted, c, v);
+    cov_finish(P + 3 * (size_t)g.p0, v.nn, __float_as_int(me.w), eps, C + 9 * (size_t)g.p0);
+}
+
+// ------------------------------------------------- SOR and the fitness score
+// (DESIGN §4 "SOR and fitness") k nearest float squared distances, no indices:
+// a max-heap of k floats per lane in LDS, entry j of lane l at h[j * 64 + l]
+// (a lane's entries are a bank apart from its neighbours': no conflicts). The
+// heap holds the k smallest distances seen whatever their order of arrival.
+struct DistHeap {
+    float pq[3];
+    float* h;  // this lane's entry 0
+    int k;
+    __device__ __forceinline__ float& at(int j) const { return h[j * GI_LANES]; }
+    // entry 0 replaced by d, sifted down within the first m entries
+    __device__ __forceinline__ void sift(float d, int m) {
+        int i = 0;
+        for (;;) {
+            const int l = 2 * i + 1;
+            if (l >= m) break;
+            const float hl = at(l), hr = l + 1 < m ? at(l + 1) : -1.f;  // distances are >= 0
+            const float hm = fmaxf(hl, hr);
+            if (!(hm > d)) break;
+            at(i) = hm;
+            i = hr > hl ? l + 1 : l;
+        }
+        at(i) = d;
+    }
+    __device__ __forceinline__ void visit(const float4 t) {
+        const float pi[3] = {t.x, t.y, t.z};
+        const float d = dist2f(pq, pi);
+        if (d < at(0)) sift(d, k);
+    }
+    __device__ __forceinline__ float kth() const { return at(0); }
+};
+
+// grid (point blocks, clouds), LDS 64 * (mean_k + 1) floats: PCL's
+// StatisticalOutlierRemoval distances[] of every cloud of more than mean_k
+// points, in point order (include/odo.h odo_cloud_sor_batch)
+__global__ __launch_bounds__(64) void k_sor_dist(const GgCloud* __restrict__ cl, const int* __restrict__ cstart,
+                                                 const float4* __restrict__ sorted, int mean_k,
+                                                 float* __restrict__ dist) {
+    extern __shared__ float sor_heap[];
+    const GgCloud g = cl[blockIdx.y];
+    const int s = blockIdx.x * 64 + threadIdx.x;
+    if (g.n <= mean_k || s >= g.n) return;
+    const float4 me = sorted[(size_t)g.p0 + s];
+    DistHeap v;
+    v.pq[0] = me.x;
+    v.pq[1] = me.y;
+    v.pq[2] = me.z;
+    v.h = sor_heap + threadIdx.x;
+    v.k = mean_k + 1;
+    for (int j = 0; j < v.k; j++) v.at(j) = __builtin_inff();
+    int c[3];
+    gg_cell3(g, v.pq, c);
+    gg_walk(g, cstart + g.c0, sorted, c, v);
+    // heap sort: ascending in entries 0 ... k - 1
+    for (int m = v.k - 1; m >= 1; m--) {
+        const float last = v.at(m);
+        v.at(m) = v.at(0);
+        v.sift(last, m);
+    }
+    double sum = 0;  // entry 0 is dropped, as PCL drops nn_dists[0]
+    // sqrtf is the correctly rounded root (hipcc's default); __fsqrt_rn is the native approximation here
+    for (int j = 1; j < v.k; j++) sum += (double)sqrtf(v.at(j));
+    dist[(size_t)g.p0 + __float_as_int(me.w)] = (float)(sum / (double)mean_k);
+}
+
+// one workgroup per cloud: sum and sq_sum over thread-strided partials and
+// block_sum256's fixed order, then PCL's mean, variance, stddev, threshold
+__global__ __launch_bounds__(GI_THREADS) void k_sor_stats(const GgCloud* __restrict__ cl,
+                                                          const float* __restrict__ dist, int mean_k,
+                                                          double stddev_mul, SorStats* __restrict__ st) {
+    __shared__ double red[2][GI_THREADS];
+    __shared__ double out[2];
+    const GgCloud g = cl[blockIdx.x];
+    if (g.n <= mean_k) return;  // skipped: the host preset st
+    double v[2] = {0, 0};
+    for (int i = threadIdx.x; i < g.n; i += GI_THREADS) {
+        const float d = dist[(size_t)g.p0 + i];
+        v[0] += (double)d;
+        v[1] += (double)(d * d);  // the product in float, as PCL's vector<float> arithmetic
+    }
+    block_sum256<2>(v, red, out);
+    if (threadIdx.x) return;
+    const double n = (double)g.n, sum = out[0], sq = out[1];
+    const double mean = sum / n, var = (sq - sum * sum / n) / (n - 1.0), sd = sqrt(var);
+    SorStats r;
+    r.sum = sum;
+    r.sq_sum = sq;
+    r.mean = mean;
+    r.stddev = sd;
+    r.threshold = mean + stddev_mul * sd;
+    r.n_out = 0;
+    r.pad = 0;
+    st[blockIdx.x] = r;
+}
+
+// grid (256-point chunks, clouds): the keep byte of every point (a NaN
+// threshold keeps all) and the chunk's kept count
+__global__ __launch_bounds__(256) void k_sor_mark(const GgCloud* __restrict__ cl, const float* __restrict__ dist,
+                                                  const SorStats* __restrict__ st, int mean_k, int nchunk,
+                                                  uint8_t* __restrict__ keep, int* __restrict__ chunk_cnt) {
+    const GgCloud g = cl[blockIdx.y];
+    if ((int)blockIdx.x * 256 >= g.n) return;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    int k = 0;
+    if (i < g.n) {
+        k = g.n <= mean_k || !((double)dist[(size_t)g.p0 + i] > st[blockIdx.y].threshold);
+        keep[(size_t)g.p0 + i] = (uint8_t)k;
+    }
+    const int tot = __syncthreads_count(k);
+    if (threadIdx.x == 0) chunk_cnt[(size_t)blockIdx.y * nchunk + blockIdx.x] = tot;
+}
+
+// one workgroup per cloud: the chunk counts become the chunks' first kept
+// ranks, their total is n_out
+__global__ __launch_bounds__(256) void k_sor_scan(const GgCloud* __restrict__ cl, int nchunk,
+                                                  int* __restrict__ chunk_cnt, SorStats* __restrict__ st) {
+    const int m = (cl[blockIdx.x].n + 255) / 256;
+    const int per = (m + 255) / 256;
+    const int begin = min(m, (int)threadIdx.x * per), end = min(m, begin + per);
+    const int tot = gg_block_scan(chunk_cnt + (size_t)blockIdx.x * nchunk, begin, end);
+    if (threadIdx.x == 0) st[blockIdx.x].n_out = tot;
+}
+
+// grid (256-point chunks, clouds): the kept rows of cloud k (16-byte points at
+// pts + row0[k], their counts alike) in order to rows new0[k] ... of the copies
+__global__ __launch_bounds__(256) void k_sor_pack(const GgCloud* __restrict__ cl, const uint8_t* __restrict__ keep,
+                                                  const int* __restrict__ chunk_cnt, int nchunk,
+                                                  const int* __restrict__ row0, const int* __restrict__ new0,
+                                                  const uint4* __restrict__ pts, const int* __restrict__ counts,
+                                                  uint4* __restrict__ pts_out, int* __restrict__ counts_out) {
+    __shared__ int wsum[4];
+    const GgCloud g = cl[blockIdx.y];
+    if ((int)blockIdx.x * 256 >= g.n) return;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    const int k = i < g.n ? keep[(size_t)g.p0 + i] : 0;
+    const uint64_t b = __ballot(k);
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    if (lane == 0) wsum[w] = __popcll(b);
+    __syncthreads();
+    int rank = chunk_cnt[(size_t)blockIdx.y * nchunk + blockIdx.x] + __popcll(b & (((uint64_t)1 << lane) - 1));
+    for (int j = 0; j < w; j++) rank += wsum[j];
+    if (!k) return;
+    const size_t from = (size_t)row0[blockIdx.y] + i, to = (size_t)new0[blockIdx.y] + rank;
+    pts_out[to] = pts[from];
+    counts_out[to] = counts[from];
+}
+
+// the nearest target distance: one float
+struct Nearest1 {
+    float pq[3];
+    float bd;
+    __device__ __forceinline__ void visit(const float4 t) {
+        const float pi[3] = {t.x, t.y, t.z};
+        bd = fminf(bd, dist2f(pq, pi));
+    }
+    __device__ __forceinline__ float kth() const { return bd; }
+};
+
+// grid (source point blocks, pairs): getFitnessScore's nearest squared distance
+// of every transformed source point over the whole target (no distance cap),
+// the source in its cell order; nn in source point order at the pair's `work`
+__global__ __launch_bounds__(64) void k_gicp_fit_nn(const GgCloud* __restrict__ cl, const GgPair* __restrict__ pairs,
+                                                    const int* __restrict__ cstart,
+                                                    const float4* __restrict__ sorted, const float* __restrict__ T,
+                                                    float* __restrict__ nn) {
+    const GgPair pr = pairs[blockIdx.y];
+    const GgCloud S = cl[pr.s], G = cl[pr.t];
+    const int s = blockIdx.x * 64 + threadIdx.x;
+    if (s >= S.n || G.n == 0) return;
+    const float4 me = sorted[(size_t)S.p0 + s];
+    const float p[3] = {me.x, me.y, me.z};
+    Nearest1 v;
+    xform4f(T + 16 * (size_t)blockIdx.y, p, v.pq);
+    v.bd = __builtin_inff();
+    int c[3];
+    gg_cell3(G, v.pq, c);
+    gg_walk(G, cstart + G.c0, sorted, c, v);
+    nn[(size_t)pr.work + __float_as_int(me.w)] = v.bd;
+}
+
+// one workgroup per pair: score = (sum of nn in block_sum256's order) / ns;
+// DBL_MAX for an empty source or target (PCL's nr == 0)
+__global__ __launch_bounds__(GI_THREADS) void k_gicp_fit_sum(const GgCloud* __restrict__ cl,
+                                                             const GgPair* __restrict__ pairs,
+                                                             const float* __restrict__ nn,
+                                                             double* __restrict__ score) {
+    __shared__ double red[1][GI_THREADS];
+    __shared__ double out[1];
+    const GgPair pr = pairs[blockIdx.x];
+    const int ns = cl[pr.s].n;
+    if (ns == 0 || cl[pr.t].n == 0) {
+        if (threadIdx.x == 0) score[blockIdx.x] = DBL_MAX;
+        return;
+    }
+    double v[1] = {0};
+    for (int i = threadIdx.x; i < ns; i += GI_THREADS) v[0] += (double)nn[(size_t)pr.work + i];
+    block_sum256<1>(v, red, out);
+    if (threadIdx.x == 0) score[blockIdx.x] = out[0] / (double)ns;
 }
 
 // the correspondence search over g.rings rings around the query's (clipped)
@@ -1096,6 +1332,38 @@ void launch_gg_cov(hipStream_t st, const float* P, const GgCloud* cl, int ncl, i
                    const float4* sorted, double* C) {
     if (ncl == 0 || max_n < 20) return;
     hipLaunchKernelGGL(k_gicp_cov_grid, dim3((max_n + 63) / 64, ncl), dim3(64), 0, st, P, cl, cstart, sorted, C, 1e-3);
+}
+
+void launch_sor(hipStream_t st, const GgCloud* cl, int ncl, int max_n, const int* cstart, const float4* sorted,
+                int mean_k, double stddev_mul, float* dist, SorStats* stats, uint8_t* keep, int* chunk_cnt) {
+    if (ncl == 0 || max_n == 0) return;
+    const int nchunk = (max_n + 255) / 256;
+    if (max_n > mean_k) {
+        hipLaunchKernelGGL(k_sor_dist, dim3((max_n + 63) / 64, ncl), dim3(64), (size_t)(mean_k + 1) * 64 * 4, st, cl,
+                           cstart, sorted, mean_k, dist);
+        hipLaunchKernelGGL(k_sor_stats, dim3(ncl), dim3(GI_THREADS), 0, st, cl, dist, mean_k, stddev_mul, stats);
+    }
+    hipLaunchKernelGGL(k_sor_mark, dim3(nchunk, ncl), dim3(256), 0, st, cl, dist, stats, mean_k, nchunk, keep,
+                       chunk_cnt);
+    hipLaunchKernelGGL(k_sor_scan, dim3(ncl), dim3(256), 0, st, cl, nchunk, chunk_cnt, stats);
+}
+
+void launch_sor_pack(hipStream_t st, const GgCloud* cl, int ncl, int max_n, const uint8_t* keep, const int* chunk_cnt,
+                     const int* row0, const int* new0, const void* pts, const int* counts, void* pts_out,
+                     int* counts_out) {
+    if (ncl == 0 || max_n == 0) return;
+    const int nchunk = (max_n + 255) / 256;
+    hipLaunchKernelGGL(k_sor_pack, dim3(nchunk, ncl), dim3(256), 0, st, cl, keep, chunk_cnt, nchunk, row0, new0,
+                       (const uint4*)pts, counts, (uint4*)pts_out, counts_out);
+}
+
+void launch_gg_fitness(hipStream_t st, const GgCloud* cl, const GgPair* pairs, int nprob, int max_ns,
+                       const int* cstart, const float4* sorted, const float* T, float* nn, double* score) {
+    if (nprob == 0) return;
+    if (max_ns)
+        hipLaunchKernelGGL(k_gicp_fit_nn, dim3((max_ns + 63) / 64, nprob), dim3(64), 0, st, cl, pairs, cstart, sorted,
+                           T, nn);
+    hipLaunchKernelGGL(k_gicp_fit_sum, dim3(nprob), dim3(GI_THREADS), 0, st, cl, pairs, nn, score);
 }
 
 void launch_gg_icp(hipStream_t st, const float* P, const GgCloud* cl, const GgPair* pairs, int nprob,

@@ -419,6 +419,27 @@ void launch_gg_icp(hipStream_t st, const float* P, const GgCloud* cl, const GgPa
                    const int* cstart, const float4* sorted, const double* C, float* outp, double* Mah, int* is,
                    int* it, const float* guess, double max_corr_dist, int max_iterations, int max_inner, float* T12,
                    int* outi);
+// StatisticalOutlierRemoval and getFitnessScore over the same grids (k_gicp.hip;
+// DESIGN §4 "SOR and fitness"). One record per cloud:
+constexpr int SOR_MAX_K = 64;  // mean_k: 65 floats per lane of LDS (PCL's default is 50)
+struct SorStats {
+    double sum, sq_sum, mean, stddev, threshold;
+    int n_out, pad;
+};
+// dist (point order, preset to 0), stats (preset: zeros) and keep of every
+// cloud; a cloud of at most mean_k points keeps all. chunk_cnt: ncl x
+// ceil(max_n / 256) ints, on return the first kept rank of every 256-point chunk
+void launch_sor(hipStream_t st, const GgCloud* cl, int ncl, int max_n, const int* cstart, const float4* sorted,
+                int mean_k, double stddev_mul, float* dist, SorStats* stats, uint8_t* keep, int* chunk_cnt);
+// the kept 16-byte rows pts[row0[k] + i] and their counts, in order, to rows
+// new0[k] ... of pts_out / counts_out (row0, new0 on the device)
+void launch_sor_pack(hipStream_t st, const GgCloud* cl, int ncl, int max_n, const uint8_t* keep, const int* chunk_cnt,
+                     const int* row0, const int* new0, const void* pts, const int* counts, void* pts_out,
+                     int* counts_out);
+// nn[pair.work + i] = the nearest squared distance of T[pair] * source point i
+// over the whole target; score[pair] = their mean, DBL_MAX for an empty side
+void launch_gg_fitness(hipStream_t st, const GgCloud* cl, const GgPair* pairs, int nprob, int max_ns,
+                       const int* cstart, const float4* sorted, const float* T, float* nn, double* score);
 // Batched ADAPTIVE_RICP / RANSAC back-ends (k_ricp.hip), on the pair stream
 // after launch_ransac. The branch rule's constants (odometry.cpp:52-53):
 struct RicpCfg {

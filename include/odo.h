@@ -695,6 +695,76 @@ int odo_gicp_dense(odo_ctx* ctx, const int32_t* pairs, int nprob, const float* g
  * NULL. Errors as odo_get_dense_cloud. */
 int odo_dense_cloud_device(odo_ctx* ctx, int i, const odo_cloud_point** d_pts, const int32_t** d_counts, int* n);
 
+/* ---- StatisticalOutlierRemoval and GICP's fitness score ----
+ * Frame::StatisticalOutlierRemovalFilterCloud(meanK, stddev) (frame.cpp:228-238,
+ * pcl::StatisticalOutlierRemoval<PointXYZRGB>) and GeneralizedICP::mScore =
+ * getFitnessScore() (generalizedicp.cpp:82) over the grids of odo_gicp_grid_*
+ * (DESIGN §4 "SOR and fitness"). PCL is restated from its source as recalled,
+ * not linked: parity with the library is unpinned.
+ *   d2(p, q)  the float squared distance of the GICP searches: ((dx * dx + dy *
+ *           dy) + dz * dz) with float differences, no fused operations.
+ *   SOR, a cloud of n points, mean_k >= 1, stddev_mul finite:
+ *     point i: the mean_k + 1 smallest d2(p_i, p_j) over all j (i included),
+ *           ascending, the first dropped (PCL's nn_dists[0]); only distances
+ *           enter, so no result depends on a tie rule or on the points' order;
+ *           dist_sum = the double sum, in ascending order, of (double)sqrtf(d2)
+ *           (a correctly rounded float root); distances[i] = (float)(dist_sum /
+ *           (double)mean_k).
+ *     cloud: sum += (double)distances[i]; sq_sum += (double)(distances[i] *
+ *           distances[i]), the product in float; mean = sum / n; variance =
+ *           (sq_sum - sum * sum / n) / (n - 1); stddev = sqrt(variance);
+ *           threshold = mean + stddev_mul * stddev. PCL sums in index order,
+ *           the device in a fixed order of its own (bit-identical run to run).
+ *     point i is removed iff (double)distances[i] > threshold: a NaN threshold
+ *           (negative computed variance) keeps every point, as in PCL. Kept
+ *           points keep their order; colours and voxel counts travel with them.
+ *     n <= mean_k (PCL reads past the end of its result vectors): the cloud is
+ *           left as it is, ODO_SOR_SKIPPED, mean = stddev = threshold = 0.
+ *     mean_k > 64: ODO_ERR_CAPACITY (PCL's default is 50).
+ *   fitness, source S (ns points), target T, transform M (row-major 4 x 4):
+ *           s' = M s as x' = ((m00 * x + m01 * y) + m02 * z) + m03 in float; nn_i
+ *           = min_j d2(s'_i, t_j) over the WHOLE target (PCL's max_range is
+ *           DBL_MAX: no distance cap, however far s' lies outside the target's
+ *           grid); score = (sum of (double)nn_i in a fixed order) / ns. An empty
+ *           source or target: DBL_MAX (PCL's nr == 0). The reference's 1e6 for
+ *           "not converged" is the caller's (include/odo_frontend.hpp does it).
+ *
+ * odo_dense_sor filters every cloud of the last dense-cloud call where it lies
+ * in HBM: the kept points and counts are packed frame after frame again and the
+ * context's offsets follow, so odo_get_dense_cloud, odo_dense_cloud_device and
+ * odo_gicp_dense then see the filtered clouds. It counts as a dense-cloud call:
+ * device pointers handed out before it are no longer valid. A second call
+ * filters the filtered clouds, as calling the reference's method twice would.
+ * info: one record per frame of that call. Synchronises the context first.
+ * ODO_ERR_STATE before any dense-cloud call; ODO_ERR_ARG (nothing changed): a
+ * null pointer, mean_k < 1, stddev_mul not finite; ODO_ERR_CAPACITY: mean_k >
+ * 64, more than 1048576 points in a cloud. */
+int odo_dense_sor(odo_ctx* ctx, int mean_k, double stddev_mul, odo_sor_info* info);
+/* The same for ncl host clouds (P packed x, y, z; offs ncl + 1 first rows, as
+ * odo_gicp_grid_covariances): keep[i] = 1 for a point that stays, distances
+ * (may be NULL) PCL's distances[] (zeros for a skipped cloud), info per cloud.
+ * cell as odo_gicp_grid_batch: 0 = chosen per cloud from n and mean_k, > 0
+ * forced (tests); no result depends on it. Capacity limits as
+ * odo_gicp_grid_covariances. ODO_ERR_ARG (nothing written): null pointers with
+ * non-zero sizes, offsets not starting at 0 or decreasing, mean_k < 1,
+ * stddev_mul or cell not finite, cell < 0, a non-finite coordinate, ncl < 0. */
+int odo_cloud_sor_batch(odo_ctx* ctx, const float* P, const int32_t* offs, int ncl, int mean_k, double stddev_mul,
+                        float cell, uint8_t* keep, float* distances, odo_sor_info* info);
+/* getFitnessScore of nprob (source, target, T) problems on host clouds laid out
+ * as odo_gicp_grid_batch's; T 16 floats per pair. score: one double per pair.
+ * nn_d2 (may be NULL, for tests): nn_i of every source point, pair after pair
+ * (zeros for a pair with an empty target). cell: 0 = chosen per cloud, > 0
+ * forced. Limits and errors as odo_gicp_grid_batch; a non-finite T entry is
+ * ODO_ERR_ARG. */
+int odo_gicp_grid_fitness(odo_ctx* ctx, const float* src, const int32_t* soffs, const float* tgt,
+                          const int32_t* toffs, const float* T, int nprob, float cell, double* score, float* nn_d2);
+/* The same for pairs of frames of the last dense-cloud call (pairs as
+ * odo_gicp_dense, T 16 floats per pair: the registration's result), on the
+ * clouds where they lie in HBM; one grid per distinct frame named. Equals
+ * odo_gicp_grid_fitness on the same points bit for bit. Errors as
+ * odo_gicp_dense. */
+int odo_gicp_dense_fitness(odo_ctx* ctx, const int32_t* pairs, int nprob, const float* T, double* score);
+
 /* Kabsch::Compute (kabsch.cpp:14): one GPU workgroup (k_kabsch: centroids, A^T B
  * with a fixed-order block reduction, 3x3 Jacobi SVD). A,B: n x 3 host arrays.
  * R = W diag(1, 1, sgn(det V det W)) V^T is a rotation for every input (the

@@ -320,6 +320,27 @@ public:
         if (!mbCloud) return;
         DenseCloud(resolution);
     }
+    // Frame::StatisticalOutlierRemovalFilterCloud (frame.cpp:228-238,
+    // pcl::StatisticalOutlierRemoval<PointXYZRGB>): without a cloud it returns
+    // (frame.cpp:230). It filters mpCloud itself (odo_cloud_sor_batch), so a
+    // second call filters the filtered cloud, as the reference. A cloud of at
+    // most meanK points is left as it is (ODO_SOR_SKIPPED; PCL is undefined there).
+    void StatisticalOutlierRemovalFilterCloud(int meanK, double stddev) {
+        if (!mbCloud) return;
+        std::vector<float> pts;
+        pts.reserve(3 * mpCloud.size());
+        for (const odo_cloud_point& p : mpCloud) pts.insert(pts.end(), {p.x, p.y, p.z});
+        const int32_t offs[2] = {0, (int32_t)mpCloud.size()};
+        std::vector<uint8_t> keep(mpCloud.size());
+        odo_sor_info info;
+        Check(odo_cloud_sor_batch(detail::shared_ctx(), pts.data(), offs, 1, meanK, stddev, 0.0f, keep.data(), nullptr,
+                                  &info),
+              "Frame::StatisticalOutlierRemovalFilterCloud");
+        size_t m = 0;
+        for (size_t i = 0; i < mpCloud.size(); ++i)
+            if (keep[i]) mpCloud[m++] = mpCloud[i];
+        mpCloud.resize(m);
+    }
     bool HasCloud() const { return mbCloud; }
     std::vector<odo_cloud_point> mpCloud;  // frame.h:80 (DenseCloud::Ptr): the points, camera frame
 
@@ -659,7 +680,10 @@ public:
 // Odometry/generalizedicp.h: GeneralizedICP(iters, maxCorrespondenceDist)
 // (generalizedicp.cpp:11-22; Odometry builds it with (10, 0.07)) and
 // Compute(source, target, guess) (generalizedicp.cpp:30-39, 65-89) over n x 3
-// clouds: mT12 = the final transformation when converged, identity otherwise.
+// clouds: mT12 = the final transformation when converged, identity otherwise;
+// mScore = getFitnessScore() of it when converged (generalizedicp.cpp:82,
+// odo_gicp_grid_fitness), 1e6 otherwise (generalizedicp.cpp:86; also where the
+// reference returns before Align: a cloud under 20 points, an empty frame cloud).
 class GeneralizedICP {
 public:
     GeneralizedICP() : GeneralizedICP(15, 0.05) {}
@@ -670,13 +694,14 @@ public:
         Check(odo_gicp(detail::shared_ctx(), source.data(), (int)(source.size() / 3), target.data(),
                        (int)(target.size() / 3), guess.data(), mIters, mDist, mT12.data(), &converged, &iters, &ncorr),
               "GeneralizedICP::Compute");
-        return converged != 0;
+        return Score(converged != 0, source, target);
     }
     // Compute(pF1, pF2, guess) (generalizedicp.cpp:41-53) over the frames' dense
     // clouds (Frame::CreateCloud / VoxelGridFilterCloud), camera frame: false
     // without running when either cloud is empty (generalizedicp.cpp:43). Whole
     // clouds go through the grid neighbour searches (odo_gicp_grid_batch).
     bool Compute(const Frame* pF1, const Frame* pF2, const Pose& guess) {
+        mScore = 1e6;
         if (pF1->mpCloud.empty() || pF2->mpCloud.empty()) return false;
         std::vector<float> pts[2];
         const Frame* fr[2] = {pF1, pF2};
@@ -689,14 +714,24 @@ public:
         Check(odo_gicp_grid_batch(detail::shared_ctx(), pts[0].data(), so, pts[1].data(), to, guess.data(), 1, mIters,
                                   mDist, 0.0f, mT12.data(), &converged, &iters, &ncorr),
               "GeneralizedICP::Compute");
-        return converged != 0;
+        return Score(converged != 0, pts[0], pts[1]);
     }
     void SetMaximumIterations(int iters) { mIters = iters; }
     void SetMaxCorrespondenceDistance(double dist) { mDist = dist; }
 
     Pose mT12 = Identity();
+    double mScore = 1e6;  // generalizedicp.h: mGicp.getFitnessScore() of mT12, 1e6 when not converged
 
 private:
+    bool Score(bool converged, const std::vector<float>& source, const std::vector<float>& target) {
+        mScore = 1e6;
+        if (!converged) return false;
+        const int32_t so[2] = {0, (int32_t)(source.size() / 3)}, to[2] = {0, (int32_t)(target.size() / 3)};
+        Check(odo_gicp_grid_fitness(detail::shared_ctx(), source.data(), so, target.data(), to, mT12.data(), 1, 0.0f,
+                                    &mScore, nullptr),
+              "GeneralizedICP::Compute");
+        return true;
+    }
     int mIters;
     double mDist;
 };

@@ -256,6 +256,18 @@ typedef struct odo_cloud_info {
     float   min_p[3], max_p[3]; /* getMinMax3D of CreateCloud's points, before Twc (zero when empty) */
 } odo_cloud_info;
 
+#define ODO_SOR_OK      0  /* the filter ran */
+#define ODO_SOR_SKIPPED 1  /* n_in <= mean_k (the empty cloud too): the cloud is left as it is */
+
+/* One cloud of odo_dense_sor / odo_cloud_sor_batch. 40 bytes. */
+typedef struct odo_sor_info {
+    int32_t status;             /* ODO_SOR_* */
+    int32_t n_in, n_out;        /* points before and after */
+    int32_t pad;
+    double  mean, stddev, threshold;  /* of distances[]; zero when skipped; stddev and threshold NaN when the
+                                         computed variance is negative (every point is then kept) */
+} odo_sor_info;
+
 #ifdef __cplusplus
 }
 #endif

@@ -106,10 +106,9 @@ __global__ void __launch_bounds__(256) k_adapt_cand(const uint8_t* __restrict__ 
             }
         }
     }
-    int2 tot;
-    const int2 base = block_scan2i(cnt, 0, reinterpret_cast<int(*)[2]>(ws), &tot);
+    int tot;
+    int o = block_exclusive_scan<0, true>(cnt, ws, &tot);
     uint32_t* out = cand + (size_t)f * cand_stride + B.cand_off;
-    int o = base.x;
     {
         int r = r0, q = q0;
         for (int i = i0; i < i1; i++) {
@@ -122,7 +121,7 @@ __global__ void __launch_bounds__(256) k_adapt_cand(const uint8_t* __restrict__ 
             }
         }
     }
-    if (threadIdx.x == 0) band_cnt[(size_t)f * nbands + blockIdx.x] = tot.x;
+    if (threadIdx.x == 0) band_cnt[(size_t)f * nbands + blockIdx.x] = tot;
     __syncthreads();
     const int hv = sh[threadIdx.x];
     if (hv) atomicAdd(&hist[((size_t)f * ncells + B.cell) * 256 + threadIdx.x], hv);
@@ -273,19 +272,7 @@ __global__ void __launch_bounds__(256) k_adapt_assemble(const uint32_t* __restri
             block_nth_element<uint32_t, ScoreKey>(A, n, retain, posL, posR, S);
             if (threadIdx.x == 0) {
                 // std::partition(begin + n_points, end, response >= ambiguous)
-                // (libstdc++ bidirectional __partition)
-                const uint32_t amb = A[retain - 1] >> 24;
-                int first = retain, last = n;
-                while (true) {
-                    while (first != last && (A[first] >> 24) >= amb) ++first;
-                    if (first == last) break;
-                    --last;
-                    while (first != last && !((A[last] >> 24) >= amb)) --last;
-                    if (first == last) break;
-                    sel_swap(A, first, last);
-                    ++first;
-                }
-                S.nl = first;
+                S.nl = gnu_partition_le<uint32_t, ScoreKey>(A, retain, n, ScoreKey::key(A[retain - 1]));
             }
             __syncthreads();
             n = S.nl;
@@ -377,20 +364,7 @@ __global__ void __launch_bounds__(256) k_adapt_select_dbg(uint32_t* A, int n, in
     block_nth_element<uint32_t, ScoreKey>(A, n, nth, posL, posR, S);
     if (threadIdx.x == 0) {
         int m = n;
-        if (mode == 1 && n > nth) {
-            const uint32_t amb = A[nth - 1] >> 24;
-            int first = nth, last = n;
-            while (true) {
-                while (first != last && (A[first] >> 24) >= amb) ++first;
-                if (first == last) break;
-                --last;
-                while (first != last && !((A[last] >> 24) >= amb)) --last;
-                if (first == last) break;
-                sel_swap(A, first, last);
-                ++first;
-            }
-            m = first;
-        }
+        if (mode == 1 && n > nth) m = gnu_partition_le<uint32_t, ScoreKey>(A, nth, n, ScoreKey::key(A[nth - 1]));
         *n_out = m;
     }
 }

@@ -252,10 +252,9 @@ __global__ void __launch_bounds__(256) k_oa_scand(const uint8_t* __restrict__ cp
             }
         }
     }
-    int2 tot;
-    const int2 base = block_scan2i(cnt, 0, reinterpret_cast<int(*)[2]>(ws), &tot);
+    int tot;
+    int o = block_exclusive_scan<0, true>(cnt, ws, &tot);
     uint32_t* out = cand + (size_t)f * cand_stride + B.cand_off;
-    int o = base.x;
     {
         int r = i0 / max(nq, 1), k = i0 - r * nq;
         for (int i = i0; i < i1; i++) {
@@ -274,7 +273,7 @@ __global__ void __launch_bounds__(256) k_oa_scand(const uint8_t* __restrict__ cp
             }
         }
     }
-    if (threadIdx.x == 0) band_cnt[(size_t)f * nbands + blockIdx.x] = tot.x;
+    if (threadIdx.x == 0) band_cnt[(size_t)f * nbands + blockIdx.x] = tot;
     __syncthreads();
     const int hv = sh[threadIdx.x];
     if (hv) atomicAdd(&hist[((size_t)f * nimgs + B.img) * 256 + threadIdx.x], hv);
@@ -306,15 +305,10 @@ __global__ void __launch_bounds__(256) k_oa_count(const int* __restrict__ hist, 
 
 // ============================================================ per-cell select
 // Float responses as ascending 32-bit keys: comp(a, b) = a.response >
-// b.response is key(a) < key(b) for key = ~ord(response), ord the
-// order-preserving map of IEEE floats (no response is -0 or NaN).
-ODO_INLINE uint32_t f_ord(float v) {
-    const uint32_t u = __float_as_uint(v);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-ODO_INLINE float f_unord(uint32_t o) { return __uint_as_float((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o); }
-ODO_INLINE uint32_t key_greater(float r) { return ~f_ord(r); }
-ODO_INLINE float resp_of_key(uint32_t k) { return f_unord(~k); }
+// b.response is key(a) < key(b) for key = ~f32_ordered(response), the
+// order-preserving map of IEEE floats (odo_wave.h) (no response is -0 or NaN).
+ODO_INLINE uint32_t key_greater(float r) { return ~f32_ordered(r); }
+ODO_INLINE float resp_of_key(uint32_t k) { return f32_unordered(~k); }
 
 struct HiKey {  // 64-bit elements ordered by their high word
     static ODO_INLINE uint32_t key(uint64_t e) { return (uint32_t)(e >> 32); }
@@ -394,7 +388,7 @@ __global__ void __launch_bounds__(256) k_oa_select(const uint32_t* __restrict__ 
         if (m > 2 * I.quota) {
             block_nth_element<uint32_t, ScoreKey>(A32, m, 2 * I.quota, posL, posR, S);
             if (threadIdx.x == 0)
-                s_n = sel_partition_le<uint32_t, ScoreKey>(A32, 2 * I.quota, m, ScoreKey::key(A32[2 * I.quota - 1]));
+                s_n = gnu_partition_le<uint32_t, ScoreKey>(A32, 2 * I.quota, m, ScoreKey::key(A32[2 * I.quota - 1]));
             __syncthreads();
             m = s_n;
         }
@@ -410,7 +404,7 @@ __global__ void __launch_bounds__(256) k_oa_select(const uint32_t* __restrict__ 
         // retainBest(quota) by Harris response
         if (m > I.quota) {
             block_nth_element<uint64_t, HiKey>(A64, m, I.quota, posL, posR, S);
-            if (threadIdx.x == 0) s_n = sel_partition_le<uint64_t, HiKey>(A64, I.quota, m, HiKey::key(A64[I.quota - 1]));
+            if (threadIdx.x == 0) s_n = gnu_partition_le<uint64_t, HiKey>(A64, I.quota, m, HiKey::key(A64[I.quota - 1]));
             __syncthreads();
             m = s_n;
         }
@@ -475,7 +469,7 @@ __global__ void __launch_bounds__(256) k_oa_assemble(const uint64_t* __restrict_
         if (retain == 0) n = 0;
         else {
             block_nth_element<uint64_t, HiKey>(A, n, retain, posL, posR, S);
-            if (threadIdx.x == 0) s_n = sel_partition_le<uint64_t, HiKey>(A, retain, n, HiKey::key(A[retain - 1]));
+            if (threadIdx.x == 0) s_n = gnu_partition_le<uint64_t, HiKey>(A, retain, n, HiKey::key(A[retain - 1]));
             __syncthreads();
             n = s_n;
         }
@@ -526,11 +520,6 @@ __global__ void __launch_bounds__(256) k_oa_assemble(const uint64_t* __restrict_
 // magic-rounded offsets (cvRound half to even), one ballot per test group.
 __constant__ int c_oumax[16] = {15, 15, 15, 15, 14, 14, 14, 13, 13, 12, 11, 10, 9, 8, 6, 3};
 __constant__ float4 c_opatf[256];  // pattern test t: (x0, y0, x1, y1)
-
-ODO_INLINE int refl101(int i, int n) {
-    while (i < 0 || i >= n) i = i < 0 ? -i : 2 * n - 2 - i;
-    return i;
-}
 
 typedef float f32x2o __attribute__((ext_vector_type(2)));
 #define OF_RND_MAGIC 12582912.0f  // 1.5 * 2^23
@@ -667,7 +656,7 @@ __global__ void __launch_bounds__(64 * OF_NW) k_oa_finalize(const uint8_t* __res
             const int yy = cy - 18 + r, xx = cx - 18 - sh2 + c;
             PBw[i] = (yy >= 0 && yy < L.h && xx >= 0 && xx < L.w)
                          ? bim[(size_t)yy * L.pitch + xx]
-                         : un[(size_t)refl101(yy, L.h) * L.pitch + refl101(xx, L.w)];
+                         : un[(size_t)reflect101(yy, L.h) * L.pitch + reflect101(xx, L.w)];
         }
     }
     __syncthreads();

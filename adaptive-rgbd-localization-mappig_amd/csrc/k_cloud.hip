@@ -33,18 +33,12 @@
 //                    The optional Twc and the 16-byte store.
 #include "odo_device.h"
 #include "odo_internal.h"
+#include "odo_wave.h"
 
 namespace odo {
 
 #define CL_ROUNDS (CLOUD_CHUNK / 64)
 #define CL_WAVES 4  // chunks (waves) per workgroup
-
-// float <-> unsigned with the same order (-0 below +0)
-ODO_INLINE uint32_t cl_ord(float f) {
-    const uint32_t b = __float_as_uint(f);
-    return b ^ ((b >> 31) ? 0xffffffffu : 0x80000000u);
-}
-ODO_INLINE float cl_unord(uint32_t u) { return __uint_as_float(u ^ ((u >> 31) ? 0x80000000u : 0xffffffffu)); }
 
 // frame.cpp:200-205; false: the pixel has no point
 ODO_INLINE bool cl_point(const uint16_t* __restrict__ D, int p, int W, const FrameCalib& k, float& x, float& y,
@@ -55,21 +49,13 @@ ODO_INLINE bool cl_point(const uint16_t* __restrict__ D, int p, int W, const Fra
     y = ((float)i - k.cy) * z * k.invfy;
     return z > 0.0f;
 }
-// lanes below this one among the set bits of m
-ODO_INLINE int cl_rank(uint64_t m) {
-    return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-}
 
 // in-place exclusive scan of v[0..n) by one wave, 64 entries a round; returns the total
 ODO_INLINE int cl_wave_scan(int32_t* __restrict__ v, int n, int lane) {
     int run = 0;
     for (int c0 = 0; c0 < n; c0 += 64) {
         const int c = c0 + lane, t = c < n ? v[c] : 0;
-        int inc = t;
-        for (int o = 1; o < 64; o <<= 1) {
-            const int u = __shfl_up(inc, o);
-            if (lane >= o) inc += u;
-        }
+        const int inc = wave_incl_scan_shfl(t, lane);
         if (c < n) v[c] = run + inc - t;
         run += __shfl(inc, 63);
     }
@@ -100,7 +86,7 @@ __global__ void __launch_bounds__(256) k_cloud_bounds(const uint16_t* __restrict
         if (p < P && cl_point(D, p, W, cal, v[0], v[1], v[2])) {
             cnt++;
             for (int a = 0; a < 3; a++) {
-                const uint32_t o = cl_ord(v[a]);
+                const uint32_t o = f32_ordered(v[a]);
                 lo[a] = min(lo[a], o);
                 hi[a] = max(hi[a], o);
             }
@@ -153,8 +139,8 @@ __global__ void __launch_bounds__(256) k_cloud_plan(CloudFrame* __restrict__ fr,
     F.pad = 0;
     if (F.n_valid > 0) {
         for (int a = 0; a < 3; a++) {
-            I.min_p[a] = cl_unord(F.lo[a]);
-            I.max_p[a] = cl_unord(F.hi[a]);
+            I.min_p[a] = f32_unordered(F.lo[a]);
+            I.max_p[a] = f32_unordered(F.hi[a]);
         }
         bool ok = leaf > 0.0f;
         if (ok) {
@@ -223,7 +209,7 @@ __global__ void __launch_bounds__(256) k_cloud_keys(const uint16_t* __restrict__
         float x = 0.f, y = 0.f, z = 0.f;
         const bool valid = p < P && cl_point(D, p, W, cal, x, y, z);
         const uint64_t m = __ballot(valid);
-        const int pos = base + cl_rank(m);
+        const int pos = base + lane_rank(m);
         base += __popcll(m);
         if (valid) {
             uint32_t k = (uint32_t)pos;
@@ -322,7 +308,7 @@ __global__ void __launch_bounds__(256) k_cloud_scatter(const CloudFrame* __restr
             const uint64_t bb = __ballot(bit);
             m &= bit ? bb : ~bb;
         }
-        const int rank = cl_rank(m);
+        const int rank = lane_rank(m);
         const int off = valid ? s_off[w][d] : 0;
         __syncthreads();
         if (valid && rank == 0) s_off[w][d] = off + __popcll(m);
@@ -368,11 +354,7 @@ __global__ void __launch_bounds__(64) k_cloud_offsets(CloudFrame* __restrict__ f
     int run = 0;
     for (int f0 = 0; f0 < n; f0 += 64) {
         const int f = f0 + lane, t = f < n ? fr[f].n_points : 0;
-        int inc = t;
-        for (int o = 1; o < 64; o <<= 1) {
-            const int u = __shfl_up(inc, o);
-            if (lane >= o) inc += u;
-        }
+        const int inc = wave_incl_scan_shfl(t, lane);
         if (f < n) fr[f].out_off = run + inc - t;
         run += __shfl(inc, 63);
     }
@@ -393,7 +375,7 @@ __global__ void __launch_bounds__(256) k_cloud_starts(const CloudFrame* __restri
         const int e = chunk * CLOUD_CHUNK + r * 64 + lane;
         const bool head = e < nv && (e == 0 || K[e] != K[e - 1]);
         const uint64_t m = __ballot(head);
-        if (head) V[base + cl_rank(m)] = (uint32_t)e;
+        if (head) V[base + lane_rank(m)] = (uint32_t)e;
         base += __popcll(m);
     }
 }

@@ -11,6 +11,7 @@
 //                 orbextractor.cpp:14-85,805-811; frame.cpp:139-164,286-313
 #include "odo_device.h"
 #include "odo_internal.h"
+#include "odo_wave.h"
 #ifdef FS_STATS
 #include <cstdio>
 #endif
@@ -166,12 +167,6 @@ constexpr int kCircleDy[16] = {3, 3, 2, 1, 0, -1, -2, -3, -3, -3, -2, -1, 0, 1, 
 #define FS_RSTRIDE (FS_RING + 8)  // a wave's ring + its trash slot (entry FS_RING), 16-byte multiple
 #define FS_CL 1024   // corner list (a level-0 segment of 7 cells: ~270); beyond it NMS and placement scan the score map
 
-ODO_INLINE void wave_lds_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 #ifdef FS_STATS
 // measurement build only: work counters of k_fast_seg, printed per launch
 __device__ unsigned long long fs_stats[8];
@@ -182,17 +177,6 @@ __device__ unsigned long long fs_stats[8];
 // a quad's 4-bit pixel mask in the compass's layout: pixel i at bit 8i + 7
 ODO_INLINE uint32_t fs_msb_mask(uint32_t b4) {
     return ((b4 & 1u) << 7) | ((b4 & 2u) << 14) | ((b4 & 4u) << 21) | ((b4 & 8u) << 28);
-}
-// inclusive prefix sum over the wave's lanes (DPP: row shifts, then the row
-// totals broadcast into the rows above)
-ODO_INLINE int wave_incl_scan(int x) {
-    x += __builtin_amdgcn_update_dpp(0, x, 0x111, 0xf, 0xf, true);   // row_shr:1
-    x += __builtin_amdgcn_update_dpp(0, x, 0x112, 0xf, 0xf, true);   // row_shr:2
-    x += __builtin_amdgcn_update_dpp(0, x, 0x114, 0xf, 0xf, true);   // row_shr:4
-    x += __builtin_amdgcn_update_dpp(0, x, 0x118, 0xf, 0xf, true);   // row_shr:8
-    x += __builtin_amdgcn_update_dpp(0, x, 0x142, 0xa, 0xf, false);  // row_bcast:15 -> rows 1, 3
-    x += __builtin_amdgcn_update_dpp(0, x, 0x143, 0xc, 0xf, false);  // row_bcast:31 -> rows 2, 3
-    return x;
 }
 struct FastMisc {
     int ncl, ovf, nl;
@@ -358,8 +342,7 @@ __global__ void __launch_bounds__(FS_TH) k_fast_seg(const uint8_t* __restrict__ 
                     int cb = 0;
                     if (lane == 0) cb = atomicAdd(&M.ncl, nco);
                     cb = __shfl(cb, 0);
-                    const int pre = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(b0 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b0, 0)) +
-                                    (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(b1 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b1, 0));
+                    const int pre = lane_rank(b0) + lane_rank(b1);
                     const int p0 = cb + pre, p1 = p0 + (c0 ? 1 : 0);
                     if (c0) { if (p0 < FS_CL) clist[p0] = (uint16_t)o0; else M.ovf = 1; }
                     if (c1) { if (p1 < FS_CL) clist[p1] = (uint16_t)o1; else M.ovf = 1; }
@@ -416,9 +399,7 @@ __global__ void __launch_bounds__(FS_TH) k_fast_seg(const uint8_t* __restrict__ 
                 for (int k = 0; k < 4; k++) {
                     const bool sv = (pass4 >> (8 * k + 7)) & 1u;
                     const uint64_t bk = __ballot(sv);
-                    const uint32_t slot =
-                        __builtin_amdgcn_mbcnt_hi((uint32_t)(bk >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bk, pos)) &
-                        (FS_RING - 1);
+                    const uint32_t slot = (uint32_t)lane_rank(bk, pos) & (FS_RING - 1);
                     uint32_t at;
                     asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(at) : "v"((uint32_t)FS_RING), "v"(slot), "s"(bk));
                     ring[at] = (uint16_t)(qoff + k);
@@ -657,8 +638,6 @@ ODO_INLINE void ot_pass(int n, int t, uint32_t (&rk)[OT_KB], int (&rn)[OT_KB], c
     }
 }
 
-ODO_INLINE int block_exclusive_scan(int v, int* tmp, int* total);
-
 // The candidates of cells [cell0, cell0 + nc) in cell order to dst[0..) (those
 // at cap and beyond are dropped); returns their number.
 ODO_INLINE int ot_gather(const uint32_t* __restrict__ cand, const int* __restrict__ cand_cnt, size_t cell0, int nc,
@@ -669,7 +648,7 @@ ODO_INLINE int ot_gather(const uint32_t* __restrict__ cand, const int* __restric
         const int c = cb + t;
         const int cnt = c < nc ? cand_cnt[cell0 + c] : 0;
         int tot;
-        const int ex = block_exclusive_scan(cnt, scan, &tot);
+        const int ex = block_exclusive_scan<OT_THREADS>(cnt, scan, &tot);
         if (c < nc) {
             // 32 candidates in flight per batch (cell rows are 16-byte aligned):
             // a load-then-store loop would wait out one memory latency per 4 keys
@@ -701,46 +680,6 @@ ODO_INLINE int ot_gather(const uint32_t* __restrict__ cand, const int* __restric
 // the node's list position (never compared: seq is unique).
 ODO_INLINE uint64_t ot_key(int cnt, int seq, int pos) {
     return ((uint64_t)(uint32_t)cnt << 40) | ((uint64_t)(uint32_t)(seq & 0xFFFFFF) << 16) | (uint64_t)(pos & 0xFFFF);
-}
-
-// Block-wide exclusive scans in threadIdx order: DPP wave scans
-// (wave_incl_scan), then the wave totals (tmp: OT_THREADS/64 ints per value)
-// in one LDS step. (Until round 5 the wave scans were __shfl_up chains: six
-// dependent ds_bpermute round trips per scan.)
-ODO_INLINE int block_exclusive_scan(int v, int* tmp, int* total) {
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int x = wave_incl_scan(v);
-    if (lane == 63) tmp[wave] = x;
-    __syncthreads();
-    int base = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < OT_THREADS / 64; w++) {
-        const int sw = tmp[w];
-        if (w < wave) base += sw;
-        tot += sw;
-    }
-    *total = tot;
-    __syncthreads();
-    return base + x - v;
-}
-// two values at once (tmp: 2 * OT_THREADS/64 ints)
-ODO_INLINE int2 block_exclusive_scan2(int a, int b, int* tmp, int2* total) {
-    constexpr int NWV = OT_THREADS / 64;
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int xa = wave_incl_scan(a), xb = wave_incl_scan(b);
-    if (lane == 63) tmp[wave] = xa, tmp[NWV + wave] = xb;
-    __syncthreads();
-    int ba = 0, bb = 0, ta = 0, tb = 0;
-#pragma unroll
-    for (int w = 0; w < NWV; w++) {
-        const int sa = tmp[w], sb = tmp[NWV + w];
-        if (w < wave) ba += sa, bb += sb;
-        ta += sa;
-        tb += sb;
-    }
-    *total = int2{ta, tb};
-    __syncthreads();
-    return int2{ba + xa - a, bb + xb - b};
 }
 
 // The tree over the n > 0 gathered keys of one (frame, level) and the best key
@@ -989,7 +928,7 @@ ODO_INLINE void ot_tree(const int n, const LevelDesc& L, char* smem, int* s_vars
                     } else s = 1;
                 }
                 int2 tp;
-                const int2 ex = block_exclusive_scan2(e | (ne << 16), s, scan, &tp);
+                const int2 ex = block_exclusive_scan2<OT_THREADS>(e | (ne << 16), s, scan, &tp);
                 if (i < S) {  // read back below by the same thread
                     iscr[i] = childBase + (ex.x & 0xFFFF);
                     npos[i * 4 + 0] = e;
@@ -1127,7 +1066,7 @@ ODO_INLINE void ot_tree(const int n, const LevelDesc& L, char* smem, int* s_vars
                 // one scan of the three counts: (e, ne) packed in 16-bit
                 // fields (each <= 4 * node_cap <= 8192), s beside them
                 int2 tp;
-                const int2 ex = block_exclusive_scan2(e | (ne << 16), s, scan, &tp);
+                const int2 ex = block_exclusive_scan2<OT_THREADS>(e | (ne << 16), s, scan, &tp);
                 const int ex_e = ex.x & 0xFFFF, ex_ne = ex.x >> 16, ex_s = ex.y;
                 const int te = tp.x & 0xFFFF, tne = tp.x >> 16, ts = tp.y;
                 if (i < S) {
@@ -1298,7 +1237,7 @@ ODO_INLINE void ot_tree(const int n, const LevelDesc& L, char* smem, int* s_vars
                         }
                     }
                     int tot;
-                    const int ex = block_exclusive_scan(e | (v << 16), scan, &tot);
+                    const int ex = block_exclusive_scan<OT_THREADS>(e | (v << 16), scan, &tot);
                     if (j < vcount) {
                         const int ei = eb + (ex & 0xFFFF) + e;
                         eincl[j] = ei;
@@ -1357,7 +1296,7 @@ ODO_INLINE void ot_tree(const int n, const LevelDesc& L, char* smem, int* s_vars
                     sv = !(j >= 0 && j < J);
                 }
                 int tot;
-                const int ex = block_exclusive_scan(sv, scan, &tot);
+                const int ex = block_exclusive_scan<OT_THREADS>(sv, scan, &tot);
                 if (sv) {
                     const int pp = EJ + sb + ex;
                     nxt[pp] = cur[i];
@@ -1494,13 +1433,6 @@ __global__ void __launch_bounds__(OT_THREADS) k_octree(const uint32_t* __restric
 #define BLUR_TY 32
 #define BLUR_IW (BLUR_TX + 8)  // staged row stride: x in [tx0-4, tx0+132)
 #define BLUR_IH (BLUR_TY + 6)
-ODO_INLINE int reflect101(int i, int n) {
-    while (i < 0 || i >= n) i = i < 0 ? -i : 2 * n - 2 - i;
-    return i;
-}
-// one reflection (|overshoot| < n): branch-free
-ODO_INLINE int reflect101_1(int i, int n) { return i < 0 ? -i : (i >= n ? 2 * n - 2 - i : i); }
-
 struct BlurTiles {
     int base[17];  // first tile of each level (prefix), base[nlevels] = total
     int tx[16];    // tiles across

@@ -45,6 +45,7 @@
 
 #include "odo_internal.h"
 #include "odo_linalg.h"
+#include "odo_wave.h"
 
 namespace odo {
 namespace {
@@ -55,8 +56,6 @@ constexpr int GI_THREADS = 256;  // the ICP / BFGS workgroup: 4 waves share ever
 constexpr int GI_WAVES = GI_THREADS / GI_LANES;
 constexpr int GI_NV = 12;        // values reduced per gradient evaluation
 constexpr int GI_STAGE = 4096;   // clouds up to this many points are staged in LDS (48 KB)
-
-__device__ __forceinline__ double s3(double a, double b, double c) { return a + (b + c); }
 
 __device__ __forceinline__ float dist2f(const float* a, const float* b) {
     float r = 0.f, d;
@@ -174,7 +173,7 @@ __device__ void inv3(const double* m, double* r) {
 #define COF(i, j) (M_(((i) + 1) % 3, ((j) + 1) % 3) * M_(((i) + 2) % 3, ((j) + 2) % 3) - \
                    M_(((i) + 1) % 3, ((j) + 2) % 3) * M_(((i) + 2) % 3, ((j) + 1) % 3))
     const double c0 = COF(0, 0), c1 = COF(1, 0), c2 = COF(2, 0);
-    const double det = s3(c0 * M_(0, 0), c1 * M_(1, 0), c2 * M_(2, 0));
+    const double det = sum3d(c0 * M_(0, 0), c1 * M_(1, 0), c2 * M_(2, 0));
     const double invdet = 1.0 / det;
 #pragma unroll
     for (int i = 0; i < 3; i++)
@@ -273,8 +272,8 @@ __device__ double gi_cost(const GiProblem& P, const double* x) {
         const double* M = P.M + 9 * si;
         double t[3];
 #pragma unroll
-        for (int i = 0; i < 3; i++) t[i] = s3(M[3 * i] * r[0], M[3 * i + 1] * r[1], M[3 * i + 2] * r[2]);
-        part += s3(r[0] * t[0], r[1] * t[1], r[2] * t[2]);
+        for (int i = 0; i < 3; i++) t[i] = sum3d(M[3 * i] * r[0], M[3 * i + 1] * r[1], M[3 * i + 2] * r[2]);
+        part += sum3d(r[0] * t[0], r[1] * t[1], r[2] * t[2]);
     }
     block_sum256<1>(&part, P.red, P.bc);
     return P.bc[0] / P.m;
@@ -296,7 +295,7 @@ __device__ void gi_grad(const GiProblem& P, const double* x, double* g) {
         const double* M = P.M + 9 * si;
         double t[3];
 #pragma unroll
-        for (int i = 0; i < 3; i++) t[i] = s3(M[3 * i] * r[0], M[3 * i + 1] * r[1], M[3 * i + 2] * r[2]);
+        for (int i = 0; i < 3; i++) t[i] = sum3d(M[3 * i] * r[0], M[3 * i + 1] * r[1], M[3 * i + 2] * r[2]);
 #pragma unroll
         for (int i = 0; i < 3; i++) part[i] += t[i];
 #pragma unroll
@@ -715,12 +714,12 @@ __device__ __forceinline__ void gicp_body(const float* __restrict__ src, int ns,
                     for (int a = 0; a < 3; a++)
 #pragma unroll
                         for (int b = 0; b < 3; b++)
-                            M[3 * a + b] = s3(R[3 * a] * C1[b], R[3 * a + 1] * C1[3 + b], R[3 * a + 2] * C1[6 + b]);
+                            M[3 * a + b] = sum3d(R[3 * a] * C1[b], R[3 * a + 1] * C1[3 + b], R[3 * a + 2] * C1[6 + b]);
 #pragma unroll
                     for (int a = 0; a < 3; a++)
 #pragma unroll
                         for (int b = 0; b < 3; b++) {
-                            tmp[3 * a + b] = s3(M[3 * a] * R[3 * b], M[3 * a + 1] * R[3 * b + 1], M[3 * a + 2] * R[3 * b + 2]);
+                            tmp[3 * a + b] = sum3d(M[3 * a] * R[3 * b], M[3 * a + 1] * R[3 * b + 1], M[3 * a + 2] * R[3 * b + 2]);
                             tmp[3 * a + b] += C2[3 * a + b];
                         }
                     double Mi[9];
@@ -739,7 +738,7 @@ __device__ __forceinline__ void gicp_body(const float* __restrict__ src, int ns,
                 if (w < wave) pre += wcnt[w];
                 tot += wcnt[w];
             }
-            const int pos = pre + __popcll(bal & ((1ull << lane) - 1ull));
+            const int pos = pre + lane_rank(bal);
             if (hit) {
                 is[pos] = i;
                 it[pos] = best;
@@ -817,12 +816,6 @@ __global__ __launch_bounds__(GI_THREADS) void k_gicp(const float* __restrict__ s
 // (DESIGN §4 "Dense GICP"; GgCloud in odo_internal.h)
 constexpr int GG_CHUNK = 4096;  // cells per scan workgroup, points per bounds workgroup
 
-// floats as uint32 whose order is the floats' order (bounds by atomicMin / Max)
-__device__ __forceinline__ uint32_t gg_encode(float f) {
-    const uint32_t b = __float_as_uint(f);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-
 __device__ __forceinline__ void gg_cell3(const GgCloud& g, const float* p, int* c) {
     const int dim[3] = {g.gx, g.gy, g.gz};
 #pragma unroll
@@ -872,8 +865,8 @@ __global__ __launch_bounds__(256) void k_gg_bounds(const float* __restrict__ P, 
     if ((threadIdx.x & (GI_LANES - 1)) == 0)
 #pragma unroll
         for (int a = 0; a < 3; a++) {
-            atomicMin(&bounds[6 * k + a], gg_encode(mn[a]));
-            atomicMax(&bounds[6 * k + 3 + a], gg_encode(mx[a]));
+            atomicMin(&bounds[6 * k + a], f32_ordered(mn[a]));
+            atomicMax(&bounds[6 * k + 3 + a], f32_ordered(mx[a]));
         }
 }
 
@@ -1183,7 +1176,7 @@ __global__ __launch_bounds__(256) void k_sor_pack(const GgCloud* __restrict__ cl
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     if (lane == 0) wsum[w] = __popcll(b);
     __syncthreads();
-    int rank = chunk_cnt[(size_t)blockIdx.y * nchunk + blockIdx.x] + __popcll(b & (((uint64_t)1 << lane) - 1));
+    int rank = chunk_cnt[(size_t)blockIdx.y * nchunk + blockIdx.x] + lane_rank(b);
     for (int j = 0; j < w; j++) rank += wsum[j];
     if (!k) return;
     const size_t from = (size_t)row0[blockIdx.y] + i, to = (size_t)new0[blockIdx.y] + rank;
@@ -1297,13 +1290,6 @@ __global__ __launch_bounds__(GI_THREADS) void k_gicp_grid(
 }
 
 }  // namespace
-
-float gg_decode(uint32_t u) {
-    const uint32_t b = (u & 0x80000000u) ? (u & 0x7fffffffu) : ~u;
-    float f;
-    memcpy(&f, &b, 4);
-    return f;
-}
 
 void launch_gg_pack(hipStream_t st, const float* src, int stride, const int* row0, const int* offs, int ncl,
                     int max_n, float* dst) {

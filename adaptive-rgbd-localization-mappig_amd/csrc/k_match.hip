@@ -9,6 +9,7 @@
 
 #include "odo_device.h"
 #include "odo_internal.h"
+#include "odo_select.h"
 
 namespace odo {
 
@@ -465,173 +466,21 @@ __global__ void __launch_bounds__(256, 3) k_knn2_f4(const uint8_t* __restrict__ 
     }
 }
 
-// ============================================================ libstdc++ std::sort emulation
+// ============================================================ std::sort, workgroup-parallel
 // Exactly the GNU introsort (std::__introsort_loop + __final_insertion_sort,
 // threshold 16, median-of-3 pivot, unguarded Hoare partition, heap fallback) on
 // 64-bit (key = distance bits, payload = position) elements compared by key
 // only: reproduces the unstable order of std::sort(vector<DMatch>) in
-// ransac.cpp:199 (App. B.4). Runs on one lane over an LDS/global array.
+// ransac.cpp:199 (App. B.4). The libstdc++ routines it calls are the ones in
+// odo_select.h; tests/pair_ref.py holds the permutation model.
 struct SortEl {
     uint32_t key;  // float bits of a non-negative distance (monotonic)
     uint32_t val;
 };
+struct SortKey {
+    static ODO_INLINE uint32_t key(const SortEl& e) { return e.key; }
+};
 
-template <typename A>
-ODO_INLINE void st_swap(A a, int i, int j) {
-    SortEl t = a[i];
-    a[i] = a[j];
-    a[j] = t;
-}
-
-template <typename A>
-ODO_INLINE void st_move_median_to_first(A a, int result, int x, int y, int z) {
-    const uint32_t ax = a[x].key, ay = a[y].key, az = a[z].key;
-    if (ax < ay) {
-        if (ay < az) st_swap(a, result, y);
-        else if (ax < az) st_swap(a, result, z);
-        else st_swap(a, result, x);
-    } else if (ax < az) st_swap(a, result, x);
-    else if (ay < az) st_swap(a, result, z);
-    else st_swap(a, result, y);
-}
-
-template <typename A>
-ODO_INLINE int st_unguarded_partition(A a, int first, int last, int pivot) {
-    const uint32_t pk = a[pivot].key;
-    while (true) {
-        while (a[first].key < pk) ++first;
-        --last;
-        while (pk < a[last].key) --last;
-        if (!(first < last)) return first;
-        st_swap(a, first, last);
-        ++first;
-    }
-}
-
-template <typename A>
-ODO_INLINE void st_adjust_heap(A a, int first, int holeIndex, int len, SortEl value) {
-    const int topIndex = holeIndex;
-    int secondChild = holeIndex;
-    while (secondChild < (len - 1) / 2) {
-        secondChild = 2 * (secondChild + 1);
-        if (a[first + secondChild].key < a[first + secondChild - 1].key) secondChild--;
-        a[first + holeIndex] = a[first + secondChild];
-        holeIndex = secondChild;
-    }
-    if ((len & 1) == 0 && secondChild == (len - 2) / 2) {
-        secondChild = 2 * (secondChild + 1);
-        a[first + holeIndex] = a[first + secondChild - 1];
-        holeIndex = secondChild - 1;
-    }
-    // __push_heap
-    int parent = (holeIndex - 1) / 2;
-    while (holeIndex > topIndex && a[first + parent].key < value.key) {
-        a[first + holeIndex] = a[first + parent];
-        holeIndex = parent;
-        parent = (holeIndex - 1) / 2;
-    }
-    a[first + holeIndex] = value;
-}
-
-template <typename A>
-ODO_INLINE void st_heap_sort_range(A a, int first, int middle, int last) {
-    // std::__partial_sort(first, middle=last, last): __heap_select + __sort_heap
-    const int len = middle - first;
-    if (len >= 2) {
-        for (int parent = (len - 2) / 2;; parent--) {
-            SortEl v = a[first + parent];
-            st_adjust_heap(a, first, parent, len, v);
-            if (parent == 0) break;
-        }
-    }
-    for (int i = middle; i < last; ++i)
-        if (a[i].key < a[first].key) {
-            SortEl v = a[i];
-            a[i] = a[first];
-            st_adjust_heap(a, first, 0, len, v);
-        }
-    for (int l2 = middle; l2 - first > 1;) {
-        --l2;
-        SortEl v = a[l2];
-        a[l2] = a[first];
-        st_adjust_heap(a, first, 0, l2 - first, v);
-    }
-}
-
-template <typename A>
-ODO_INLINE void st_insertion_sort(A a, int first, int last) {
-    if (first == last) return;
-    for (int i = first + 1; i != last; ++i) {
-        SortEl val = a[i];
-        if (val.key < a[first].key) {
-            for (int k = i; k > first; --k) a[k] = a[k - 1];
-            a[first] = val;
-        } else {
-            int next = i - 1, cur = i;
-            while (val.key < a[next].key) {
-                a[cur] = a[next];
-                cur = next;
-                --next;
-            }
-            a[cur] = val;
-        }
-    }
-}
-
-template <typename A>
-ODO_INLINE void st_unguarded_insertion_sort(A a, int first, int last) {
-    for (int i = first; i != last; ++i) {
-        SortEl val = a[i];
-        int next = i - 1, cur = i;
-        while (val.key < a[next].key) {
-            a[cur] = a[next];
-            cur = next;
-            --next;
-        }
-        a[cur] = val;
-    }
-}
-
-template <typename A>
-ODO_INLINE void gnu_sort(A a, int n) {
-    if (n < 2) return;
-    // __introsort_loop with an explicit stack (recursion on the right part)
-    int lg = 31 - __builtin_clz((unsigned)n);
-    int stk_first[64], stk_last[64], stk_depth[64];
-    int sp = 0;
-    stk_first[sp] = 0;
-    stk_last[sp] = n;
-    stk_depth[sp] = 2 * lg;
-    sp++;
-    while (sp > 0) {
-        sp--;
-        int first = stk_first[sp], last = stk_last[sp], depth = stk_depth[sp];
-        while (last - first > 16) {
-            if (depth == 0) {
-                st_heap_sort_range(a, first, last, last);
-                break;
-            }
-            --depth;
-            const int mid = first + (last - first) / 2;
-            st_move_median_to_first(a, first, first + 1, mid, last - 1);
-            const int cut = st_unguarded_partition(a, first + 1, last, first);
-            // recurse on [cut, last) first (it is processed before the left loop
-            // continues in libstdc++, but the two ranges are disjoint, so order
-            // of processing does not change the result)
-            stk_first[sp] = cut;
-            stk_last[sp] = last;
-            stk_depth[sp] = depth;
-            sp++;
-            last = cut;
-        }
-    }
-    if (n > 16) {
-        st_insertion_sort(a, 0, 16);
-        st_unguarded_insertion_sort(a, 16, n);
-    } else st_insertion_sort(a, 0, n);
-}
-
-// ---- workgroup-parallel std::sort (identical permutation to gnu_sort) -------
 // Level-synchronous introsort: every range of a level is partitioned at once.
 // A Hoare partition (pivot key pk at `first`) swaps the k-th element from the
 // left with key >= pk against the k-th from the right with key <= pk for all
@@ -648,37 +497,11 @@ struct PSortRanges {
     int gs[PS_MAXR], ge[PS_MAXR], ls[PS_MAXR], le[PS_MAXR], cut[PS_MAXR];
     int nf[2 * PS_MAXR], nd[2 * PS_MAXR];
     int nr;
-    int ws[16][2];
+    int ws[32];
 };
 
 static inline size_t psort_lds_bytes(int pw) {
     return (size_t)pw * (8 + 2 + 2 + 2 + 1) + sizeof(PSortRanges) + 64;
-}
-
-// exclusive block scan of two per-thread counts
-ODO_INLINE int2 block_scan2(int a, int b, int (*ws)[2]) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    int ia = a, ib = b;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int x = __shfl_up(ia, o), y = __shfl_up(ib, o);
-        if (lane >= o) {
-            ia += x;
-            ib += y;
-        }
-    }
-    if (lane == 63) {
-        ws[w][0] = ia;
-        ws[w][1] = ib;
-    }
-    __syncthreads();
-    int ba = 0, bb = 0;
-    for (int k = 0; k < w; k++) {
-        ba += ws[k][0];
-        bb += ws[k][1];
-    }
-    __syncthreads();
-    return make_int2(ba + ia - a, bb + ib - b);
 }
 
 // range of position j (j in [f+1, l) of an active range), or -1
@@ -721,11 +544,13 @@ ODO_INLINE void block_gnu_sort(SortEl* A, int n, uint8_t* work, PSortRanges& R) 
         for (int r = t; r < nr; r += T) {
             const int f = R.f[r], l = R.l[r], d = R.d[r];
             if (d == 0) {
-                st_heap_sort_range(A, f, l, l);
+                // std::__partial_sort(first, last, last)
+                gnu_heap_select<SortEl, SortKey>(A, f, l, l);
+                gnu_sort_heap<SortEl, SortKey>(A, f, l);
                 R.d[r] = -1;
             } else {
                 R.d[r] = d - 1;
-                st_move_median_to_first(A, f, f + 1, f + (l - f) / 2, l - 1);
+                gnu_move_median_to_first<SortEl, SortKey>(A, f, f + 1, f + (l - f) / 2, l - 1);
                 R.pk[r] = (int)A[f].key;
                 R.ks[r] = 0;
             }
@@ -745,7 +570,8 @@ ODO_INLINE void block_gnu_sort(SortEl* A, int n, uint8_t* work, PSortRanges& R) 
             cg += k >= pk;
             cl += k <= pk;
         }
-        const int2 base = block_scan2(cg, cl, R.ws);
+        int2 tot;
+        const int2 base = block_exclusive_scan2<0, true>(cg, cl, R.ws, &tot);
         int rg = base.x, rl = base.y;
         for (int j = j0; j < j1; j++) {
             const int r = rid[j];
@@ -821,8 +647,8 @@ ODO_INLINE void block_gnu_sort(SortEl* A, int n, uint8_t* work, PSortRanges& R) 
         const int q0 = min(m2, t * cc), q1 = min(m2, q0 + cc);
         int cnt = 0;
         for (int q = q0; q < q1; q++) cnt += R.nf[q] >= 0;
-        const int2 nb = block_scan2(cnt, 0, R.ws);
-        int o = nb.x;
+        int nnext;
+        const int o = block_exclusive_scan<0, true>(cnt, R.ws, &nnext);
         int nf_[8], nl_[8], nd_[8], nq = 0;
         for (int q = q0; q < q1; q++) {
             if (R.nf[q] < 0) continue;
@@ -838,7 +664,7 @@ ODO_INLINE void block_gnu_sort(SortEl* A, int n, uint8_t* work, PSortRanges& R) 
             R.l[o + i] = nl_[i];
             R.d[o + i] = nd_[i];
         }
-        if (t == T - 1) R.nr = o + nq;
+        if (t == 0) R.nr = nnext;
         __syncthreads();
     }
     // __final_insertion_sort == stable sort inside each final range
@@ -975,8 +801,7 @@ __global__ void __launch_bounds__(PM_THREADS) k_vo_lm(const float* __restrict__ 
             tot += s_w[w];
         }
         if (keep)
-            qlist[(size_t)p * kp_cap + base + before +
-                  __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0))] = i;
+            qlist[(size_t)p * kp_cap + base + before + lane_rank(bal)] = i;
         base += tot;
         __syncthreads();
     }

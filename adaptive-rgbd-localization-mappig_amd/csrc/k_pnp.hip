@@ -7,6 +7,7 @@
 // (deterministic run to run; agrees with the sequential oracle to rounding).
 #include "odo_device.h"
 #include "odo_internal.h"
+#include "odo_wave.h"
 
 // a * b + c as one fused multiply-add in this file's FP64 arithmetic (the
 // library builds with -ffp-contract=off for its bit-exact stages; PnP's and
@@ -692,7 +693,7 @@ __global__ void __launch_bounds__(PNP_NT, PNP_WAVES_PER_EU) k_pnp(const int32_t*
         }
         __syncthreads();
         if (has) {
-            const int k = ne + before + __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0));
+            const int k = ne + before + lane_rank(bal);
             const int s = src[i];
             const float zw = X1[3 * s + 2];
             E.X[3 * k] = X1[3 * s];

@@ -27,6 +27,7 @@
 
 #include "odo_device.h"
 #include "odo_internal.h"
+#include "odo_wave.h"
 
 namespace odo {
 
@@ -143,12 +144,6 @@ ODO_INLINE void lds_sync() {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
-
-ODO_INLINE void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 ODO_INLINE void gen_raw(int32_t* st, int32_t& f, int32_t& r, uint32_t* out, int n) {
@@ -613,10 +608,6 @@ ODO_INLINE void stage_pt(const TfcSlab& L, int q, const GoodPt& g) {
     L.row(6)[q] = g.w;
 }
 
-ODO_INLINE uint32_t lane_rank(uint64_t bal) {
-    return __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0));
-}
-
 // PCL TransformationFromCorrespondences::add over the slab's n points,
 // bit-identical to the serial add(): lane 0 runs the accumulated-weight
 // prefix, all lanes form alpha = w/acc in parallel, then lane (i,j) < 9 runs
@@ -662,14 +653,14 @@ ODO_INLINE void tfc_fold(const TfcSlab& L, int nin, int lane, float& acc, float&
         }
         acc = a;
     }
-    wave_sync();
+    wave_lds_sync();
     TP(0)
     for (int k = lane; k < nin; k += 64) {
         const float al = L.row(6)[k] / L.row(7)[k];
         L.row(6)[k] = al;
         L.row(7)[k] = 1.0f - al;
     }
-    wave_sync();
+    wave_lds_sync();
     TP(1)
     if (lane < 9) {
         const int i = lane / 3, j = lane - 3 * (lane / 3);
@@ -718,7 +709,7 @@ ODO_INLINE void tfc_fold(const TfcSlab& L, int nin, int lane, float& acc, float&
         m2 = a2;
         c = cc;
     }
-    wave_sync();
+    wave_lds_sync();
     TP(2)
 #undef TP
 }
@@ -992,7 +983,7 @@ ODO_INLINE void eval_hyps(const RansacBufs& B, const RansacCfg& cfg, int p, int 
                 }
                 const uint64_t bal = __ballot(in);
                 if (in) stage_pt(TS, lane_rank(bal), g);
-                wave_sync();
+                wave_lds_sync();
                 nfit += __popcll(bal);
                 tfc_fold(TS, __popcll(bal), lane, tacc, tm1, tm2, tc, TPP);
             } else {
@@ -1011,14 +1002,14 @@ ODO_INLINE void eval_hyps(const RansacBufs& B, const RansacCfg& cfg, int p, int 
                     const int cnt = __popcll(bal);
                     nfit += cnt;
                     if (nfill + cnt > TFC_CAP) {
-                        wave_sync();
+                        wave_lds_sync();
                         tfc_fold(TS, nfill, lane, tacc, tm1, tm2, tc, TPP);
                         nfill = 0;
                     }
                     if (in) stage_pt(TS, nfill + lane_rank(bal), g);
                     nfill += cnt;
                 }
-                wave_sync();
+                wave_lds_sync();
                 tfc_fold(TS, nfill, lane, tacc, tm1, tm2, tc, TPP);
             }
             RP_ACC(t_tfc);
@@ -1066,11 +1057,11 @@ ODO_INLINE void eval_hyps(const RansacBufs& B, const RansacCfg& cfg, int p, int 
                     L.nw[c0 >> 5] = (uint32_t)bal;
                     if (c0 + 32 < ng) L.nw[(c0 >> 5) + 1] = (uint32_t)(bal >> 32);
                 }
-                wave_sync();
+                wave_lds_sync();
                 const int nin = __popcll(bal);
                 if (lane == 0) meanError = fold_dv(L, nin, meanError);
                 cnt += (unsigned)nin;
-                wave_sync();
+                wave_lds_sync();
             }
             meanError = __shfl(meanError, 0);
             RP_ACC(t_sweep);
@@ -1096,7 +1087,7 @@ ODO_INLINE void eval_hyps(const RansacBufs& B, const RansacCfg& cfg, int p, int 
                 refinedError = meanError;
                 refinedCnt = cnt;
                 for (int w = lane; w < words; w += 64) L.cur[w] = L.nw[w];
-                wave_sync();
+                wave_lds_sync();
                 useSample = false;
                 if (cnt == prev) break;
             } else break;
@@ -1146,7 +1137,7 @@ ODO_INLINE void eval_hyps(const RansacBufs& B, const RansacCfg& cfg, int p, int 
             __hip_atomic_store(B.ready + (size_t)p * B.hcap + h, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
             if (!B.no_fold) try_fold(B, cfg, p);
         }
-        wave_sync();
+        wave_lds_sync();
 #ifdef ODO_RANSAC_PROFILE
         if (lane == 0 && h < RPROF_MAX) g_rprof[(size_t)h * 8 + 7] = wall_clock64();  // after ready + fold
 #endif
@@ -1194,7 +1185,7 @@ __global__ void __launch_bounds__(256) k_ransac_open(RansacBufs B, int npairs) {
             if (w < (int)(threadIdx.x >> 6)) before += s_cnt[w];
             tot += s_cnt[w];
         }
-        if (open) B.open_list[s_base + before + (int)lane_rank(bal)] = p;
+        if (open) B.open_list[s_base + before + lane_rank(bal)] = p;
         __syncthreads();
         if (threadIdx.x == 0) s_base += tot;
         __syncthreads();
@@ -1326,12 +1317,7 @@ ODO_INLINE void lanes_body(const RansacBufs& B, const RansacCfg& cfg, uint32_t* 
         for (int i0 = 0; i0 < cnt && mine < 0; i0 += 64) {
             const int i = i0 + lane;
             const int w = i < cnt ? B.st[B.open_list[i]].ng + 1 : 0;
-            int incl = w;
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const int t = __shfl_up(incl, o);
-                if (lane >= o) incl += t;
-            }
+            const int incl = wave_incl_scan_shfl(w, lane);
             const int c0 = carry + incl - w, c1 = carry + incl;
             const int st = i + (int)((long long)spare * c0 / tot), en = i + 1 + (int)((long long)spare * c1 / tot);
             const uint64_t hit = __ballot(i < cnt && st <= gw && gw < en);
@@ -1405,9 +1391,9 @@ ODO_INLINE void lanes_body(const RansacBufs& B, const RansacCfg& cfg, uint32_t* 
                 GoodPt gq = lane < ng ? P[lane] : GoodPt{};
                 uint32_t q0 = inset ? cw[lane] : 0u, q1 = inset && 32 < ng ? cw[64 + lane] : 0u;
                 for (int c0 = 0; c0 < ng; c0 += 64) {
-                    wave_sync();  // the previous chunk has been read
+                    wave_lds_sync();  // the previous chunk has been read
                     lp[lane] = gq;
-                    wave_sync();
+                    wave_lds_sync();
                     const uint32_t b0 = q0, b1 = q1;
                     if (c0 + 64 < ng) {
                         const int c1 = c0 + 64, w1 = c1 >> 5;
@@ -1473,7 +1459,7 @@ ODO_INLINE void lanes_body(const RansacBufs& B, const RansacCfg& cfg, uint32_t* 
             uint32_t* nw = slab + (size_t)(cur ^ 1) * B.mask_words * 64;
             const uint64_t actm = __ballot(act);
             const int nact = __popcll(actm);
-            const int rank = (int)lane_rank(actm);  // this lane's slot among the active ones
+            const int rank = lane_rank(actm);  // this lane's slot among the active ones
             if (act) la[rank] = lane;
             // the active hypotheses' transforms in slot order, read back by the
             // sweep as broadcast 16-byte loads per slot instead of permutes
@@ -1486,7 +1472,7 @@ ODO_INLINE void lanes_body(const RansacBufs& B, const RansacCfg& cfg, uint32_t* 
 #pragma unroll
                 for (int i = 0; i < 6; i += 2) *reinterpret_cast<double2*>(tw + 12 + i) = double2{Z[i], Z[i + 1]};
             }
-            wave_sync();
+            wave_lds_sync();
             double meanError = 0.0;
             unsigned c = 0;
             const int pj = lane & 31, hf = lane >> 5;
@@ -1516,7 +1502,7 @@ ODO_INLINE void lanes_body(const RansacBufs& B, const RansacCfg& cfg, uint32_t* 
                     if (a < nact) lres[a * LN_RS + pj] = d;
                 }
                 LP(const uint64_t lp_cb = wall_clock64(); lp_inner += lp_cb - lp_ca;)
-                wave_sync();
+                wave_lds_sync();
                 uint32_t word = 0;
                 if (act) {
                     const int nj = min(32, ng - c0);
@@ -1548,7 +1534,7 @@ ODO_INLINE void lanes_body(const RansacBufs& B, const RansacCfg& cfg, uint32_t* 
                     }
                     nw[(size_t)(c0 >> 5) * 64 + lane] = word;
                 }
-                wave_sync();
+                wave_lds_sync();
                 LP(lp_sum += wall_clock64() - lp_cb;)
             }
             LP(lp_sweep += wall_clock64() - lp_q; lp_q = wall_clock64();)
@@ -1894,7 +1880,7 @@ __global__ void __launch_bounds__(256) k_hyp_payload(RansacBufs B, const odo_ran
                 tot += s_wc[w];
             }
             if (in) {
-                const int r = before + (int)lane_rank(bal);
+                const int r = before + lane_rank(bal);
                 const odo_dmatch m = good[k];
                 int* o = payload + HYP_PAYLOAD_HDR + 4 * r;
                 o[0] = m.queryIdx;

@@ -12,6 +12,7 @@
 // Nothing here reads a count on the host: the grids are sized by the batch and
 // match_cap, the kernels read n_matches / n_good / res / T12 on the device.
 #include "odo_internal.h"
+#include "odo_wave.h"
 
 namespace odo {
 
@@ -129,8 +130,7 @@ __global__ void __launch_bounds__(RI_THREADS) k_ricp_gather(const odo_dmatch* __
         }
         __syncthreads();
         if (keep) {
-            const int k = tail + before +
-                          __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0));
+            const int k = tail + before + lane_rank(bal);
             if (k < len) {  // len is k_pair_match's count of the same filter
                 for (int j = 0; j < 3; j++) {
                     S[3 * k + j] = s[j];

@@ -6,6 +6,7 @@
 // device, their bounds (one host round trip: the grids are sized from them),
 // the counting sort, the covariances once per cloud, the ICP workgroups.
 #include "odo_ctx.h"
+#include "odo_wave.h"
 
 namespace odo {
 
@@ -164,8 +165,8 @@ int build_grids(odo_ctx* c, const Source& src, const std::vector<int32_t>& offs,
         float mn[3], mx[3];
         const int n = offs[k + 1] - offs[k];
         for (int a = 0; a < 3; a++) {
-            mn[a] = gg_decode(hb[6 * (size_t)k + a]);
-            mx[a] = gg_decode(hb[6 * (size_t)k + 3 + a]);
+            mn[a] = f32_unordered(hb[6 * (size_t)k + a]);
+            mx[a] = f32_unordered(hb[6 * (size_t)k + 3 + a]);
             if (n && (!std::isfinite(mn[a]) || !std::isfinite(mx[a])))
                 return fail(ODO_ERR_DEVICE, std::string(who) + ": a cloud holds a non-finite coordinate");
         }

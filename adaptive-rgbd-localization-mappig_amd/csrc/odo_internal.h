@@ -404,9 +404,8 @@ struct GgPair {
 void launch_gg_pack(hipStream_t st, const float* src, int stride, const int* row0, const int* offs, int ncl,
                     int max_n, float* dst);
 // bounds[6 * k]: min x, y, z and max x, y, z of cloud k as ordered uint32
-// (gg_decode), preset to 0xffffffff / 0 by the caller; offs ncl + 1 (device)
+// (f32_ordered, odo_wave.h), preset to 0xffffffff / 0 by the caller; offs ncl + 1 (device)
 void launch_gg_bounds(hipStream_t st, const float* P, const int* offs, int ncl, int max_n, uint32_t* bounds);
-float gg_decode(uint32_t u);
 // counting sort of every cloud by cell: cnt and fill (ncells_total + 1 each) are
 // preset to 0; cnt becomes cstart, bsum holds (ncells_total + 1 + 4095) / 4096 ints
 void launch_gg_build(hipStream_t st, const float* P, const GgCloud* cl, int ncl, int max_n, int64_t ncells_total,

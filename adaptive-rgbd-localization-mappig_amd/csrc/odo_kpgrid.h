@@ -7,6 +7,7 @@
 
 #include "odo_device.h"
 #include "odo_internal.h"
+#include "odo_wave.h"
 
 namespace odo {
 
@@ -75,11 +76,7 @@ ODO_INLINE void lmk_bin(const float* __restrict__ K, int n, const LmGrid& G, int
         const int per = (ncells + 63) / 64, c0 = min((int)threadIdx.x * per, ncells), c1 = min(c0 + per, ncells);
         int sum = 0;
         for (int c = c0; c < c1; c++) sum += s_cnt[c];
-        int inc = sum;
-        for (int o = 1; o < 64; o <<= 1) {
-            const int t = __shfl_up(inc, o);
-            if ((int)threadIdx.x >= o) inc += t;
-        }
+        const int inc = wave_incl_scan_shfl(sum, (int)threadIdx.x);
         int run = inc - sum;
         for (int c = c0; c < c1; c++) {
             const int t = s_cnt[c];

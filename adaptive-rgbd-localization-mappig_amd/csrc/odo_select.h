@@ -1,65 +1,16 @@
-// Workgroup-wide helpers shared by the ADAPTIVE grid extractors
-// (k_adaptive.hip: FAST inner detector; k_adaptive_orb.hip: cv::ORB inner
-// detector): ordered ranks and scans over the workgroup, the threshold-free
-// FAST S map of one 128 x 8 tile, and libstdc++'s std::nth_element /
-// std::partition restated as workgroup-parallel code over any element type
-// with a 32-bit ascending key.
+// The threshold-free FAST S map of one 128 x 8 tile (the ADAPTIVE grid
+// extractors, k_adaptive.hip and k_adaptive_orb.hip), and the one home of the
+// libstdc++ <algorithm> internals this project restates: the routines whose
+// exact tie behaviour its bit parity rests on, over any element type T with
+// an ascending 32-bit key K::key(e). The workgroup-parallel std::nth_element
+// is here; the workgroup-parallel std::sort built on the same routines is
+// block_gnu_sort in k_match.hip.
 #pragma once
 
 #include "odo_device.h"
+#include "odo_wave.h"
 
 namespace odo {
-
-// ============================================================ block helpers
-// ordered rank of `keep` among the workgroup's threads (thread order) and the
-// total; ws: >= 16 ints of LDS
-ODO_INLINE int block_rank(bool keep, int* ws, int* total) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
-    const uint64_t b = __ballot(keep);
-    const int in_wave = __popcll(b & ((1ull << lane) - 1ull));
-    if (lane == 0) ws[wv] = __popcll(b);
-    __syncthreads();
-    int base = 0, tot = 0;
-    for (int k = 0; k < nw; k++) {
-        const int c = ws[k];
-        if (k < wv) base += c;
-        tot += c;
-    }
-    __syncthreads();
-    *total = tot;
-    return base + in_wave;
-}
-
-// exclusive scan of two per-thread counts over the workgroup
-ODO_INLINE int2 block_scan2i(int a, int b, int (*ws)[2], int2* total) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
-    int ia = a, ib = b;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int x = __shfl_up(ia, o), y = __shfl_up(ib, o);
-        if (lane >= o) {
-            ia += x;
-            ib += y;
-        }
-    }
-    if (lane == 63) {
-        ws[wv][0] = ia;
-        ws[wv][1] = ib;
-    }
-    __syncthreads();
-    int ba = 0, bb = 0, ta = 0, tb = 0;
-    for (int k = 0; k < nw; k++) {
-        if (k < wv) {
-            ba += ws[k][0];
-            bb += ws[k][1];
-        }
-        ta += ws[k][0];
-        tb += ws[k][1];
-    }
-    __syncthreads();
-    *total = make_int2(ta, tb);
-    return make_int2(ba + ia - a, bb + ib - b);
-}
 
 // ============================================================ S map tile
 // S(p) = the best 9-arc contrast of p (FAST at threshold t keeps p iff
@@ -164,27 +115,29 @@ ODO_INLINE void smap_tile(const uint8_t* __restrict__ img, int w, int h, int pit
     *reinterpret_cast<uint32_t*>(smap + (size_t)y * pitch + x) = out;
 }
 
-// ============================================================ std::nth_element
-// libstdc++ __introselect over elements of type T ordered by an ascending
-// 32-bit key K::key(e) (comp(a, b) = key(a) < key(b)). Every partition runs
-// on the whole workgroup: the Hoare scan pairs the k-th left stop
-// (key >= pk) with the k-th right stop (key <= pk) while they have not
-// crossed (k < k*), and cuts at min(L[k*], R[k*-1]) (the model checked
-// against the real std::nth_element in tests/test_adaptive_model.py).
-struct SelState {
-    int first, last, depth, pk, ks, nl, nr, done;
-    int ws[16][2];
-};
-
+// ============================================================ libstdc++ internals
+// bits/stl_algo.h and bits/stl_heap.h with comp(a, b) = K::key(a) < K::key(b),
+// on A[first, last) by one lane.
 template <typename T>
-ODO_INLINE void sel_swap(T* A, int i, int j) {
+ODO_INLINE void gnu_swap(T* A, int i, int j) {
     const T t = A[i];
     A[i] = A[j];
     A[j] = t;
 }
 
+// std::__move_median_to_first(result, x, y, z)
 template <typename T, typename K>
-ODO_INLINE void sel_adjust_heap(T* A, int first, int hole, int len, T value) {
+ODO_INLINE void gnu_move_median_to_first(T* A, int result, int x, int y, int z) {
+    const uint32_t kx = K::key(A[x]), ky = K::key(A[y]), kz = K::key(A[z]);
+    int m;
+    if (kx < ky) m = ky < kz ? y : (kx < kz ? z : x);
+    else m = kx < kz ? x : (ky < kz ? z : y);
+    gnu_swap(A, result, m);
+}
+
+// std::__adjust_heap with its __push_heap
+template <typename T, typename K>
+ODO_INLINE void gnu_adjust_heap(T* A, int first, int hole, int len, T value) {
     const int top = hole;
     int child = hole;
     while (child < (len - 1) / 2) {
@@ -207,25 +160,38 @@ ODO_INLINE void sel_adjust_heap(T* A, int first, int hole, int len, T value) {
     A[first + hole] = value;
 }
 
-// std::__heap_select(first, middle, last) (depth-limit fallback; one lane)
+// std::__heap_select(first, middle, last): the depth-limit fallback of
+// nth_element, and with middle = last the first half of sort's
 template <typename T, typename K>
-ODO_INLINE void sel_heap_select(T* A, int first, int middle, int last) {
+ODO_INLINE void gnu_heap_select(T* A, int first, int middle, int last) {
     const int len = middle - first;
     if (len >= 2)
         for (int parent = (len - 2) / 2;; parent--) {
-            sel_adjust_heap<T, K>(A, first, parent, len, A[first + parent]);
+            gnu_adjust_heap<T, K>(A, first, parent, len, A[first + parent]);
             if (parent == 0) break;
         }
     for (int i = middle; i < last; ++i)
         if (K::key(A[i]) < K::key(A[first])) {  // __pop_heap(first, middle, i)
             const T v = A[i];
             A[i] = A[first];
-            sel_adjust_heap<T, K>(A, first, 0, len, v);
+            gnu_adjust_heap<T, K>(A, first, 0, len, v);
         }
 }
 
+// std::__sort_heap(first, last)
 template <typename T, typename K>
-ODO_INLINE void sel_insertion_sort(T* A, int first, int last) {
+ODO_INLINE void gnu_sort_heap(T* A, int first, int last) {
+    while (last - first > 1) {
+        --last;
+        const T v = A[last];
+        A[last] = A[first];
+        gnu_adjust_heap<T, K>(A, first, 0, last - first, v);
+    }
+}
+
+// std::__insertion_sort(first, last)
+template <typename T, typename K>
+ODO_INLINE void gnu_insertion_sort(T* A, int first, int last) {
     if (first == last) return;
     for (int i = first + 1; i != last; ++i) {
         const T v = A[i];
@@ -243,6 +209,36 @@ ODO_INLINE void sel_insertion_sort(T* A, int first, int last) {
         }
     }
 }
+
+// std::partition(A + first, A + last, key <= amb) (the bidirectional
+// __partition): the tail step of KeyPointsFilter::retainBest, whose predicate
+// response >= ambiguous is key <= key(ambiguous) for a key that orders by
+// response descending. Returns the partition point.
+template <typename T, typename K>
+ODO_INLINE int gnu_partition_le(T* A, int first, int last, uint32_t amb) {
+    while (true) {
+        while (first != last && K::key(A[first]) <= amb) ++first;
+        if (first == last) break;
+        --last;
+        while (first != last && !(K::key(A[last]) <= amb)) --last;
+        if (first == last) break;
+        gnu_swap(A, first, last);
+        ++first;
+    }
+    return first;
+}
+
+// ============================================================ std::nth_element
+// libstdc++ __introselect over elements of type T ordered by an ascending
+// 32-bit key K::key(e) (comp(a, b) = key(a) < key(b)). Every partition runs
+// on the whole workgroup: the Hoare scan pairs the k-th left stop
+// (key >= pk) with the k-th right stop (key <= pk) while they have not
+// crossed (k < k*), and cuts at min(L[k*], R[k*-1]) (the model checked
+// against the real std::nth_element in tests/test_adaptive_model.py).
+struct SelState {
+    int first, last, depth, pk, ks, nl, nr, done;
+    int ws[32];
+};
 
 // comp(a, b) = score(a) > score(b) (ResponseComparator /
 // KeypointResponseGreater) on packed FAST keypoints (score << 24 | y << 12 |
@@ -268,8 +264,8 @@ ODO_INLINE void block_nth_element(T* A, int n, int nth, int* posL, int* posR, Se
         const int first = S.first, last = S.last;
         if (S.depth == 0) {
             if (t == 0) {
-                sel_heap_select<T, K>(A, first, nth + 1, last);
-                sel_swap(A, first, nth);
+                gnu_heap_select<T, K>(A, first, nth + 1, last);
+                gnu_swap(A, first, nth);
                 S.done = 1;
             }
             __syncthreads();
@@ -277,13 +273,7 @@ ODO_INLINE void block_nth_element(T* A, int n, int nth, int* posL, int* posR, Se
         }
         if (t == 0) {
             S.depth--;
-            // __move_median_to_first(first, first + 1, mid, last - 1)
-            const int a = first + 1, b = first + (last - first) / 2, c = last - 1;
-            const uint32_t ka = K::key(A[a]), kb = K::key(A[b]), kc = K::key(A[c]);
-            int m;
-            if (ka < kb) m = kb < kc ? b : (ka < kc ? c : a);
-            else m = ka < kc ? a : (kb < kc ? c : b);
-            sel_swap(A, first, m);
+            gnu_move_median_to_first<T, K>(A, first, first + 1, first + (last - first) / 2, last - 1);
             S.pk = (int)K::key(A[first]);
         }
         __syncthreads();
@@ -298,7 +288,7 @@ ODO_INLINE void block_nth_element(T* A, int n, int nth, int* posL, int* posR, Se
             cl += k <= pk;
         }
         int2 tot;
-        const int2 base = block_scan2i(cg, cl, S.ws, &tot);
+        const int2 base = block_exclusive_scan2<0, true>(cg, cl, S.ws, &tot);
         int rg = base.x, rl = base.y;
         for (int j = j0; j < j1; j++) {
             const uint32_t k = K::key(A[j]);
@@ -318,7 +308,7 @@ ODO_INLINE void block_nth_element(T* A, int n, int nth, int* posL, int* posR, Se
         }
         __syncthreads();
         const int ks = S.ks;
-        for (int k = t; k < ks; k += NT) sel_swap(A, posL[k], posR[k]);
+        for (int k = t; k < ks; k += NT) gnu_swap(A, posL[k], posR[k]);
         __syncthreads();
         if (t == 0) {
             int cut = ks < tot.x ? posL[ks] : last;
@@ -328,26 +318,8 @@ ODO_INLINE void block_nth_element(T* A, int n, int nth, int* posL, int* posR, Se
         }
         __syncthreads();
     }
-    if (t == 0 && !S.done) sel_insertion_sort<T, K>(A, S.first, S.last);
+    if (t == 0 && !S.done) gnu_insertion_sort<T, K>(A, S.first, S.last);
     __syncthreads();
-}
-
-// std::partition(A + first, A + last, key <= amb) (libstdc++ bidirectional
-// __partition; one lane): the tail step of KeyPointsFilter::retainBest, whose
-// predicate response >= ambiguous is key <= key(ambiguous) for a key that
-// orders by response descending. Returns the partition point.
-template <typename T, typename K>
-ODO_INLINE int sel_partition_le(T* A, int first, int last, uint32_t amb) {
-    while (true) {
-        while (first != last && K::key(A[first]) <= amb) ++first;
-        if (first == last) break;
-        --last;
-        while (first != last && !(K::key(A[last]) <= amb)) --last;
-        if (first == last) break;
-        sel_swap(A, first, last);
-        ++first;
-    }
-    return first;
 }
 
 }  // namespace odo

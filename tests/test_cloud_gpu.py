@@ -261,6 +261,29 @@ def test_blocks_regrow_and_results_repeat():
         two.close()
 
 
+def test_more_than_64_frames():
+    """66 frames in one call: the frames' output offsets are scanned 64 at a
+    time by one wave, so frames 64 and 65 start at the carry of the first
+    round. A few scattered points per frame (none in some, also at the round's
+    edges), every frame compared with the reference like the single cases."""
+    pkg = load_pkg()
+    rng = np.random.default_rng(0x66F)
+    n = 66
+    counts = [int(k) for k in rng.integers(0, 70, n)]
+    counts[0], counts[63], counts[64], counts[65] = 3, 0, 65, 2
+    depth = np.concatenate([R.scattered(rng, k) for k in counts])
+    bgr = np.ascontiguousarray(np.broadcast_to(R.colours(rng), (n, R.H, R.W, 3)))
+    odo = pkg.Odometry(pkg.default_config(R.W, R.H, n, nfeatures=500, iterations=50,
+                                          calib={**R.CAMS["fr1"], **F.NO_DISTORTION}))
+    try:
+        info, clouds = run(odo, bgr, depth, 0.03)
+        assert [int(v) for v in info["n_valid"]] == counts
+        for f, r in enumerate(R.dense_ref(bgr, depth, R.CAMS["fr1"], 0.03)):
+            check_frame(info[f], clouds[f][0], clouds[f][1], r, f"frame {f} of {n}")
+    finally:
+        odo.close()
+
+
 def test_tracking_is_undisturbed(ctx):
     """The pair records of two tracked batches are the same with a dense-cloud
     call between them (and one before and after) as without."""

@@ -176,7 +176,8 @@ def test_bad_arguments_are_refused_with_the_outputs_untouched(pkg):
 @pytest.mark.parametrize("name,keys", R.SORT_ALONE, ids=[n for n, _ in R.SORT_ALONE])
 def test_sort_alone_at_the_depth_limit(pkg, name, keys):
     """odo_debug_sort on McIlroy's adversary inputs: ranges reach depth 0 and
-    block_gnu_sort heap-sorts them (st_heap_sort_range / st_adjust_heap). The
+    block_gnu_sort heap-sorts them (gnu_heap_select + gnu_sort_heap over
+    gnu_adjust_heap, odo_select.h). The
     reference is pair_ref.std_sort, which test_pair_ref.py holds against the
     real std::sort on these very inputs."""
     keys = np.array(keys(), np.float32)

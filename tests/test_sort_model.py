@@ -37,7 +37,7 @@ def parallel_introsort_model(keys, heaps=None):
     while ranges:
         nxt = []
         for f, l, d in ranges:
-            if d == 0:  # st_heap_sort_range: sorted for good, no children
+            if d == 0:  # heap select + sort heap: sorted for good, no children
                 heaps.append(l - f)
                 perm = pair_ref.heap_sort(k[f:l])
                 k[f:l], v[f:l] = [k[f + i] for i in perm], [v[f + i] for i in perm]

@@ -27,11 +27,9 @@
 #include "odo_device.h"
 #include "odo_internal.h"
 #include "odo_select.h"
-#include "../../include/odo_orb_pattern.h"
+#include "odo_orb_patch.h"
 
 namespace odo {
-
-__constant__ int8_t c_apattern[1024];
 
 // ============================================================ S map
 // Tile: 128 x 8 output pixels of the pitched level 0 (smap_tile, odo_select.h).
@@ -300,12 +298,11 @@ __global__ void __launch_bounds__(256) k_adapt_assemble(const uint32_t* __restri
 }
 
 // ============================================================ finalize
-// Four keypoints per wave, 16 lanes each: rBRIEF (16 tests per lane, one
-// ballot per test group) at the fixed angle -1 deg (cos/sin precomputed on the
-// host in the reference's float arithmetic); undistort + depth follow in
-// k_kp_geometry (k_finalize.hip).
-#define AF_KPW 4
-#define AF_KPB (4 * AF_KPW)
+// odo_orb_patch.h's lane layout, packed pattern and descriptor store: rBRIEF
+// (16 tests per lane) sampled straight from global memory at the fixed angle
+// -1 deg (cos/sin precomputed on the host in the reference's float
+// arithmetic); undistort + depth follow in k_kp_geometry (k_finalize.hip).
+#define AF_KPB (4 * ORB_KPW)
 __global__ void __launch_bounds__(256) k_adapt_finalize(const uint8_t* __restrict__ blur, size_t pyr_stride, int pitch,
                                                         const uint32_t* __restrict__ akp, int akp_stride,
                                                         const int* __restrict__ nkp, float ca, float sb,
@@ -317,32 +314,22 @@ __global__ void __launch_bounds__(256) k_adapt_finalize(const uint8_t* __restric
     const int g = lane >> 4, sub = lane & 15;
     const int n = nkp[f];
     if (blockIdx.x * AF_KPB >= n) return;  // whole workgroup idle
-    const int idx = blockIdx.x * AF_KPB + wave * AF_KPW + g;
+    const int idx = blockIdx.x * AF_KPB + wave * ORB_KPW + g;
     const bool valid = idx < n;
     const uint32_t key = valid ? akp[(size_t)f * akp_stride + idx] : (40u | (40u << 12));
     const int kx = (int)(key & 0xfff), ky = (int)((key >> 12) & 0xfff);
     const float a = ca, b = sb;
     const uint8_t* center = blur + (size_t)f * pyr_stride + (size_t)ky * pitch + kx;
     int tv0[16], tv1[16];
+    uint32_t pat8[16];
+    orb_lane_pattern(sub, pat8);
 #pragma unroll
     for (int w = 0; w < 16; w++) {
-        const int bit = w * 16 + sub;
-        const float x0 = (float)c_apattern[4 * bit + 0], y0 = (float)c_apattern[4 * bit + 1];
-        const float x1 = (float)c_apattern[4 * bit + 2], y1 = (float)c_apattern[4 * bit + 3];
-        tv0[w] = center[cv_round(x0 * b + y0 * a) * pitch + cv_round(x0 * a - y0 * b)];
-        tv1[w] = center[cv_round(x1 * b + y1 * a) * pitch + cv_round(x1 * a - y1 * b)];
+        const float4 Pt = orb_test_points(pat8[w]);  // (x0, y0, x1, y1)
+        tv0[w] = center[cv_round(Pt.x * b + Pt.y * a) * pitch + cv_round(Pt.x * a - Pt.y * b)];
+        tv1[w] = center[cv_round(Pt.z * b + Pt.w * a) * pitch + cv_round(Pt.z * a - Pt.w * b)];
     }
-#pragma unroll
-    for (int w = 0; w < 16; w++) {
-        const uint64_t bal = __ballot(tv0[w] < tv1[w]);
-        if (lane == 0) s_bal[wave][w] = bal;
-    }
-    __syncthreads();
-    if (valid && sub < 8) {
-        const uint32_t lo = (uint32_t)(s_bal[wave][2 * sub] >> (16 * g)) & 0xffffu;
-        const uint32_t hi = (uint32_t)(s_bal[wave][2 * sub + 1] >> (16 * g)) & 0xffffu;
-        reinterpret_cast<uint32_t*>(desc + ((size_t)f * kp_cap + idx) * 32)[sub] = lo | (hi << 16);
-    }
+    orb_store_desc(tv0, tv1, s_bal, wave, lane, valid, desc, f, kp_cap, idx);
     if (valid && sub == 0) {
         orb_kp* kp = kps + (size_t)f * kp_cap + idx;
         const float px = (float)kx, py = (float)ky;
@@ -370,10 +357,6 @@ __global__ void __launch_bounds__(256) k_adapt_select_dbg(uint32_t* A, int n, in
 }
 
 // ============================================================ launch wrappers
-void upload_adaptive_constants() {
-    hipMemcpyToSymbol(HIP_SYMBOL(c_apattern), ODO_ORB_PATTERN, sizeof(ODO_ORB_PATTERN));
-}
-
 void launch_adapt_smap(hipStream_t st, const uint8_t* pyr, size_t pyr_stride, int w, int h, int pitch, uint8_t* smap,
                        size_t smap_stride, int nframes) {
     const int tx = (pitch + SM_TW - 1) / SM_TW, ty = (h + SM_TH - 1) / SM_TH;

@@ -34,7 +34,7 @@
 #include "odo_device.h"
 #include "odo_internal.h"
 #include "odo_select.h"
-#include "../../include/odo_orb_pattern.h"
+#include "odo_orb_patch.h"
 
 namespace odo {
 
@@ -503,34 +503,20 @@ __global__ void __launch_bounds__(256) k_oa_assemble(const uint64_t* __restrict_
 }
 
 // ============================================================ finalize
-// Four keypoints per wave, 16 lanes each, OF_NW waves per workgroup (the
-// k_finalize_lds scheme, k_finalize.hip): each keypoint's two patches are
-// staged in LDS by its 16 lanes with row-contiguous dword loads -
-//   the IC disc, rows y-15..y+15 of the keypoint's cell level (always inside:
-//   runByImageBorder(15)), 9 dwords each;
-//   the rBRIEF window, rows cy-18..cy+18 of the frame pyramid's blurred level
-//   around the centre cvRound(pt / scale), 10 dwords each, written over the
-//   disc once the angle is known (its loads in flight meanwhile). A window that
-//   leaves the level is staged byte by byte with computeOrbDescriptors'
-//   border: the unblurred level at the REFLECT_101 position (the bordered
-//   pyramid's border, which the in-place ROI blur leaves untouched).
-// IC angle (ICAngles, orb.cpp): lane s sums disc rows s-15 and s+1 with
-// v_dot4 against the column weights and the |v| masks; 16-lane butterfly.
-// rBRIEF (computeOrbDescriptors): 16 tests per lane read as LDS bytes at the
-// magic-rounded offsets (cvRound half to even), one ballot per test group.
-__constant__ int c_oumax[16] = {15, 15, 15, 15, 14, 14, 14, 13, 13, 12, 11, 10, 9, 8, 6, 3};
-__constant__ float4 c_opatf[256];  // pattern test t: (x0, y0, x1, y1)
-
-typedef float f32x2o __attribute__((ext_vector_type(2)));
-#define OF_RND_MAGIC 12582912.0f  // 1.5 * 2^23
-#define OF_RND_BITS 0x4B400000u
-#define OF_IC_W 9
-#define OF_IC_N (31 * OF_IC_W)
-#define OF_BR_W 10
-#define OF_BR_N (37 * OF_BR_W)
-#define OF_KP_DW OF_BR_N  // the rBRIEF window overlays the IC disc
+// OF_NW waves per workgroup on the lane layout, tables, LDS strides and
+// per-keypoint code of odo_orb_patch.h (ICAngles: orb_ic_angle;
+// computeOrbDescriptors: orb_brief_samples, orb_store_desc). Each keypoint's
+// two patches are staged in LDS by its 16 lanes with row-contiguous dword loads -
+//   the IC disc from the keypoint's cell level (always inside:
+//   runByImageBorder(15));
+//   the rBRIEF window from the frame pyramid's blurred level around the centre
+//   cvRound(pt / scale), written over the disc once the angle is known (its
+//   loads in flight meanwhile). A window that leaves the level is staged byte
+//   by byte with computeOrbDescriptors' border: the unblurred level at the
+//   REFLECT_101 position (the bordered pyramid's border, which the in-place
+//   ROI blur leaves untouched).
 #define OF_NW 2
-#define OF_KPB (4 * OF_NW)
+#define OF_KPB (ORB_KPW * OF_NW)
 __global__ void __launch_bounds__(64 * OF_NW) k_oa_finalize(const uint8_t* __restrict__ pyr,
                                                             const uint8_t* __restrict__ blur, size_t pyr_stride,
                                                             const LevelDesc* __restrict__ lv,
@@ -541,25 +527,15 @@ __global__ void __launch_bounds__(64 * OF_NW) k_oa_finalize(const uint8_t* __res
                                                             const int* __restrict__ nkp, orb_kp* __restrict__ kps,
                                                             uint8_t* __restrict__ desc, int kp_cap) {
     __shared__ uint64_t s_bal[OF_NW][16];
-    __shared__ __attribute__((aligned(16))) uint32_t s_disc[16][8];
-    __shared__ __attribute__((aligned(16))) uint32_t s_patch[OF_NW * 4][OF_KP_DW];
-    for (int d = threadIdx.x; d < 128; d += 64 * OF_NW) {
-        const int av = d >> 3, i = d & 7;
-        const int um = c_oumax[av];
-        uint32_t m = 0;
-#pragma unroll
-        for (int bb = 0; bb < 4; bb++) {
-            const int u = 4 * i + bb - 15;
-            if (u >= -um && u <= um) m |= 0xffu << (8 * bb);
-        }
-        s_disc[av][i] = m;
-    }
+    __shared__ __attribute__((aligned(16))) uint32_t s_disc[16][ORB_DISC_W];
+    __shared__ __attribute__((aligned(16))) uint32_t s_patch[OF_KPB][ORB_KP_DW];
+    orb_load_disc(s_disc, 64 * OF_NW);
     const int f = blockIdx.y;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int g = lane >> 4, sub = lane & 15;
     const int n = nkp[f];
     if (blockIdx.x * OF_KPB >= n) return;  // uniform over the workgroup
-    const int kslot = wave * 4 + g;
+    const int kslot = wave * ORB_KPW + g;
     const int idx = blockIdx.x * OF_KPB + kslot;
     const bool valid = idx < n;
     // an invalid slot stages a dummy in-level patch (keypoint 0) and writes nothing
@@ -581,78 +557,40 @@ __global__ void __launch_bounds__(64 * OF_NW) k_oa_finalize(const uint8_t* __res
         uint32_t v[18];
 #pragma unroll
         for (int j = 0; j < 18; j++) {
-            const int i = min(sub + 16 * j, OF_IC_N - 1);
-            const int r = i / OF_IC_W, c = i - r * OF_IC_W;
+            const int i = min(sub + 16 * j, ORB_IC_N - 1);
+            const int r = i / ORB_IC_W, c = i - r * ORB_IC_W;
             v[j] = *reinterpret_cast<const uint32_t*>(img + (size_t)r * I.pitch + 4 * c);
         }
 #pragma unroll
         for (int j = 0; j < 18; j++)
-            if (sub + 16 * j < OF_IC_N) P[sub + 16 * j] = v[j];
+            if (sub + 16 * j < ORB_IC_N) P[sub + 16 * j] = v[j];
     }
-    // the rBRIEF window overlays the IC disc once the angle is known (the
-    // k_finalize_lds FIN_OVERLAY scheme): its in-level dwords are loaded now and
-    // held in registers, a window past the level edge is staged afterwards
+    // the rBRIEF window overlays the IC disc once the angle is known: its
+    // in-level dwords are loaded now and held in registers, a window past the
+    // level edge is staged afterwards
     const uint8_t* bim = blur + (size_t)f * pyr_stride + L.off;
     uint32_t vbr[24];
     if (inside) {
         const uint8_t* b0 = bim + (size_t)(cy - 18) * L.pitch + (cx - 18 - sh2);
 #pragma unroll
         for (int j = 0; j < 24; j++) {
-            const int i = min(sub + 16 * j, OF_BR_N - 1);
-            const int r = i / OF_BR_W, c = i - r * OF_BR_W;
+            const int i = min(sub + 16 * j, ORB_BR_N - 1);
+            const int r = i / ORB_BR_W, c = i - r * ORB_BR_W;
             vbr[j] = *reinterpret_cast<const uint32_t*>(b0 + (size_t)r * L.pitch + 4 * c);
         }
     }
     __syncthreads();  // s_disc, the patches
-    int m10, m01;
-    {
-        const bool has1 = sub < 15;
-        const int v0 = sub - 15, v1 = has1 ? sub + 1 : 0;
-        const uint32_t* r0 = P + (v0 + 15) * OF_IC_W;
-        const uint32_t* r1 = P + (v1 + 15) * OF_IC_W;
-        uint32_t w0[9], w1[9];
-#pragma unroll
-        for (int i = 0; i < 9; i++) {
-            w0[i] = r0[i];
-            w1[i] = r1[i];
-        }
-        const uint4* M0 = reinterpret_cast<const uint4*>(s_disc[-v0]);
-        const uint4* M1 = reinterpret_cast<const uint4*>(s_disc[v1]);
-        const uint4 a0 = M0[0], a1 = M0[1], b0 = M1[0], b1 = M1[1];
-        const uint32_t z = has1 ? 0xffffffffu : 0u;
-        const uint32_t mk0[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
-        const uint32_t mk1[8] = {b0.x & z, b0.y & z, b0.z & z, b0.w & z, b1.x & z, b1.y & z, b1.z & z, b1.w & z};
-        uint32_t s0 = 0, s1 = 0, t = 0;
-#pragma unroll
-        for (int i = 0; i < 8; i++) {
-            const uint32_t U = (uint32_t)(4 * i + 1) | ((uint32_t)(4 * i + 2) << 8) | ((uint32_t)(4 * i + 3) << 16) |
-                               ((uint32_t)(4 * i + 4) << 24);
-            const uint32_t d0 = __builtin_amdgcn_alignbyte(w0[i + 1], w0[i], sh) & mk0[i];
-            const uint32_t d1 = __builtin_amdgcn_alignbyte(w1[i + 1], w1[i], sh) & mk1[i];
-            s0 = __builtin_amdgcn_udot4(d0, 0x01010101u, s0, false);
-            s1 = __builtin_amdgcn_udot4(d1, 0x01010101u, s1, false);
-            t = __builtin_amdgcn_udot4(d0, U, t, false);
-            t = __builtin_amdgcn_udot4(d1, U, t, false);
-        }
-        m10 = (int)t - 16 * (int)(s0 + s1);
-        m01 = v0 * (int)s0 + v1 * (int)s1;
-    }
-#pragma unroll
-    for (int off = 8; off > 0; off >>= 1) {
-        m10 += __shfl_xor(m10, off);
-        m01 += __shfl_xor(m01, off);
-    }
-    const float angle = fast_atan2((float)m01, (float)m10);
+    const float angle = orb_ic_angle(P, sh, s_disc, sub);
     __syncthreads();  // every IC disc read
     if (inside) {
 #pragma unroll
         for (int j = 0; j < 24; j++)
-            if (sub + 16 * j < OF_BR_N) P[sub + 16 * j] = vbr[j];
+            if (sub + 16 * j < ORB_BR_N) P[sub + 16 * j] = vbr[j];
     } else {
         const uint8_t* un = pyr + (size_t)f * pyr_stride + L.off;
         uint8_t* PBw = reinterpret_cast<uint8_t*>(P);
-        for (int i = sub; i < 4 * OF_BR_N; i += 16) {
-            const int r = i / (4 * OF_BR_W), c = i - r * (4 * OF_BR_W);
+        for (int i = sub; i < 4 * ORB_BR_N; i += 16) {
+            const int r = i / (4 * ORB_BR_W), c = i - r * (4 * ORB_BR_W);
             const int yy = cy - 18 + r, xx = cx - 18 - sh2 + c;
             PBw[i] = (yy >= 0 && yy < L.h && xx >= 0 && xx < L.w)
                          ? bim[(size_t)yy * L.pitch + xx]
@@ -660,37 +598,9 @@ __global__ void __launch_bounds__(64 * OF_NW) k_oa_finalize(const uint8_t* __res
         }
     }
     __syncthreads();
-    const float ang = angle * (float)(3.14159265358979323846 / 180.f);
-    double sd, cd;
-    sincos((double)ang, &sd, &cd);
-    const float a = (float)cd, b = (float)sd;
-    const f32x2o BA = {b, a}, AB = {a, b}, MAG = {OF_RND_MAGIC, OF_RND_MAGIC};
-    const uint8_t* PB = reinterpret_cast<const uint8_t*>(P);
-    const uint32_t cofs = (uint32_t)(18 * 4 * OF_BR_W + 18 + sh2) - OF_RND_BITS * (uint32_t)(4 * OF_BR_W + 1);
     int tv0[16], tv1[16];
-#pragma unroll
-    for (int w = 0; w < 16; w++) {
-        const float4 Pt = c_opatf[w * 16 + sub];
-        f32x2o q0 = (f32x2o){Pt.x, Pt.x} * BA + (f32x2o){Pt.y, -Pt.y} * AB;
-        f32x2o q1 = (f32x2o){Pt.z, Pt.z} * BA + (f32x2o){Pt.w, -Pt.w} * AB;
-        q0 = q0 + MAG;
-        q1 = q1 + MAG;
-        const uint32_t o0 = __float_as_uint(q0.x) * (uint32_t)(4 * OF_BR_W) + __float_as_uint(q0.y) + cofs;
-        const uint32_t o1 = __float_as_uint(q1.x) * (uint32_t)(4 * OF_BR_W) + __float_as_uint(q1.y) + cofs;
-        tv0[w] = PB[o0];
-        tv1[w] = PB[o1];
-    }
-#pragma unroll
-    for (int w = 0; w < 16; w++) {
-        const uint64_t bal = __ballot(tv0[w] < tv1[w]);
-        if (lane == 0) s_bal[wave][w] = bal;
-    }
-    __syncthreads();
-    if (valid && sub < 8) {
-        const uint32_t lo = (uint32_t)(s_bal[wave][2 * sub] >> (16 * g)) & 0xffffu;
-        const uint32_t hi = (uint32_t)(s_bal[wave][2 * sub + 1] >> (16 * g)) & 0xffffu;
-        reinterpret_cast<uint32_t*>(desc + ((size_t)f * kp_cap + idx) * 32)[sub] = lo | (hi << 16);
-    }
+    orb_brief_samples(P, sh2, orb_rotation(angle), sub, tv0, tv1);
+    orb_store_desc(tv0, tv1, s_bal, wave, lane, valid, desc, f, kp_cap, idx);
     if (valid && sub == 0) {
         orb_kp* kp = kps + (size_t)f * kp_cap + idx;
         kp->x = px;
@@ -704,14 +614,6 @@ __global__ void __launch_bounds__(64 * OF_NW) k_oa_finalize(const uint8_t* __res
 }
 
 // ============================================================ launch wrappers
-void upload_adaptive_orb_constants() {
-    float4 pat[256];
-    for (int t = 0; t < 256; t++)
-        pat[t] = make_float4((float)ODO_ORB_PATTERN[4 * t], (float)ODO_ORB_PATTERN[4 * t + 1],
-                             (float)ODO_ORB_PATTERN[4 * t + 2], (float)ODO_ORB_PATTERN[4 * t + 3]);
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(c_opatf), pat, sizeof(pat));
-}
-
 void launch_oa_pyr(hipStream_t st, const uint8_t* pyr, size_t pyr_stride, int gpitch, const OaCell* cells, int ncells,
                    const OaImg* imgs, int buf0, int buf1, uint8_t* cpyr, size_t cp_stride, int nframes) {
     const size_t lds = (size_t)buf0 + buf1;

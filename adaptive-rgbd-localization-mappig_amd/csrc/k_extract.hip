@@ -2007,9 +2007,6 @@ __global__ void __launch_bounds__(PYR_TH) PYR_ATTR k_pyramid(const uint8_t* __re
     __syncthreads();
 }
 
-// ============================================================ host-side launch helpers
-void upload_extract_constants() { upload_finalize_constants(); }
-
 }  // namespace odo
 
 // ============================================================ launch wrappers

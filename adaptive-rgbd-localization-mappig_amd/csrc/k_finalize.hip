@@ -6,83 +6,32 @@
 // :286-313).
 //
 //   k_finalize_lds  16 lanes per keypoint, 4 keypoints per wave, both patches
-//                   staged in LDS:
-//                   IC angle from 9 aligned dwords per disc row (two rows per
-//                   lane), realigned with alignbyte, bytes outside the disc
-//                   masked, and the moments by udot4 (exact integers);
-//                   rBRIEF with the rotation in packed fp32 and cvRound by the
-//                   1.5*2^23 magic add, one ballot per test group
+//                   staged in LDS; IC angle, rBRIEF and the descriptor store
+//                   as odo_orb_patch.h describes them
 //   k_kp_geometry   one keypoint per lane: undistortion (5 double iterations)
 //                   and the depth back-projection, shared with the ADAPTIVE
 //                   extractor's finalisation (k_adaptive.hip)
 #include "odo_device.h"
 #include "odo_internal.h"
+#include "odo_orb_patch.h"
 #ifndef ODO_EXTRACT_PRIO
 #define ODO_EXTRACT_PRIO 0
 #endif
-#include "../../include/odo_orb_pattern.h"
 
 namespace odo {
 
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
-// ORB_SLAM2 pattern test t = (x0, y0, x1, y1) as signed bytes, lane-major:
-// c_pat8[s * 16 + w] = test w * 16 + s (k_finalize_lds lane s's sixteen tests
-// in 64 contiguous bytes)
-__constant__ uint32_t c_pat8[256];
-// IC_Angle disc masks: row |v|'s dword i has byte bb set (0xff) where column
-// u = 4 i + bb - 15 lies inside the disc, |u| <= umax[|v|]. A compile-time
-// table: every workgroup copies it to LDS with one load per thread (until
-// round 10 each rebuilt it from the half-widths, ~27 VALU per wave)
-struct DiscTab {
-    uint32_t m[16 * 8];
-};
-constexpr DiscTab make_disc_tab() {
-    constexpr int umax[16] = {15, 15, 15, 15, 14, 14, 14, 13, 13, 12, 11, 10, 9, 8, 6, 3};
-    DiscTab T{};
-    for (int av = 0; av < 16; av++)
-        for (int i = 0; i < 8; i++) {
-            uint32_t m = 0;
-            for (int bb = 0; bb < 4; bb++) {
-                const int u = 4 * i + bb - 15;
-                if (u >= -umax[av] && u <= umax[av]) m |= 0xffu << (8 * bb);
-            }
-            T.m[av * 8 + i] = m;
-        }
-    return T;
-}
-__constant__ DiscTab c_disc = make_disc_tab();
-
-// 1.5 * 2^23: for |x| < 2^22, the float sum x + RND_MAGIC is x rounded half to
-// even (cvRound) plus the magic, so its low mantissa bits are the integer.
-#define RND_MAGIC 12582912.0f
-#define RND_BITS 0x4B400000u
-
-#define FIN_KPW 4  // keypoints per wave
-
-// k_finalize_lds: each keypoint's two patches are
-// staged in LDS by its 16 lanes with row-contiguous dword loads (the IC disc,
-// rows ky-15..ky+15 of the level, 9 dwords each; the rBRIEF window, rows
-// ky-18..ky+18 of the blurred level, 10 dwords each: rotated pattern points
-// round into [-18, 18]). Per-lane global loads would put the 16 lanes of a
+// k_finalize_lds: each keypoint's two patches (the IC disc of the level, the
+// rBRIEF window of the blurred level) are staged in LDS by its 16 lanes with
+// row-contiguous loads. Per-lane global loads would put the 16 lanes of a
 // keypoint on 16 different rows, 64 cache lines per wave instruction through
 // the texture path; staged, a wave instruction touches about two rows per
 // keypoint, and the 512 rBRIEF samples become LDS byte reads.
-#define FL_IC_W 9                    // dwords per staged IC row
-#define FL_IC_N (31 * FL_IC_W)       // 279
-#define FL_BR_W 10                   // dwords per staged rBRIEF row
-#define FL_BR_N (37 * FL_BR_W)       // 370
-// The rBRIEF window overwrites the IC disc once the angle is known (its loads
-// are in flight since the start), so a keypoint holds 370 dwords of LDS
-// instead of 649 and more workgroups fit a CU (round 2).
-// dwords of LDS per keypoint, padded to 16 mod 32 (round 5): a wave's lanes
-// 0-31 are two keypoints whose IC rows sit 9 dwords apart ({9s mod 32} for
-// the 16 lanes: half the banks); the second keypoint 16 banks further takes
-// exactly the other half ({16 + 9s}), where the unpadded 370 (18 mod 32)
-// shared 14 of 16 banks with the first (PMC: 35.7 M conflict cycles, 1.4x
-// the kernel's LDS cycles, round 4)
-#define FL_KP_RAW FL_BR_N
-#define FL_KP_DW (((FL_KP_RAW + 15) / 32) * 32 + 16)
+// The tables, strides, rotation and descriptor store are odo_orb_patch.h's.
+// The IC moment block and the rBRIEF sample loop are written out here, the
+// text (and comments) of orb_ic_angle and orb_brief_samples there: a helper's
+// loops are unrolled before it is inlined, and the kernel then compiles to
+// other device text (three VALU per sample address instead of v_mad_u32_u24 +
+// v_add3_u32). A change to either copy belongs in both.
 template <int NW>  // waves (of 4 keypoints) per workgroup: 2 ships (a plain kernel compiles to other device text)
 __global__ void __launch_bounds__(64 * NW) k_finalize_lds(const uint8_t* __restrict__ pyr, const uint8_t* __restrict__ blur,
                                                       size_t pyr_stride, const LevelDesc* __restrict__ lv, int nlevels,
@@ -91,11 +40,9 @@ __global__ void __launch_bounds__(64 * NW) k_finalize_lds(const uint8_t* __restr
                                                       int* __restrict__ nkp, int kp_cap, uint32_t gx_rcp) {
     if (ODO_EXTRACT_PRIO) __builtin_amdgcn_s_setprio(ODO_EXTRACT_PRIO);
     __shared__ uint64_t s_bal[NW][16];
-    // disc masks, rows padded to 12 dwords: the 16 lanes of a ds_read_b128
-    // group read 16 different rows, which at 8 dwords met on 2 banks each
-    __shared__ __attribute__((aligned(16))) uint32_t s_disc[16][12];
-    __shared__ __attribute__((aligned(16))) uint32_t s_patch[NW * FIN_KPW][FL_KP_DW];
-    for (int d = threadIdx.x; d < 128; d += 64 * NW) s_disc[d >> 3][d & 7] = c_disc.m[d];
+    __shared__ __attribute__((aligned(16))) uint32_t s_disc[16][ORB_DISC_W];
+    __shared__ __attribute__((aligned(16))) uint32_t s_patch[NW * ORB_KPW][ORB_KP_DW];
+    orb_load_disc(s_disc, 64 * NW);
     // XCD remap (workgroup h runs on XCD h & 7: the eight XCDs take eight
     // contiguous runs of the (frame, block) list). gx_rcp = ceil(2^32 /
     // gridDim.x) from the host, exact for lid * gridDim.x < 2^32 (0: no
@@ -112,8 +59,8 @@ __global__ void __launch_bounds__(64 * NW) k_finalize_lds(const uint8_t* __restr
     }
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int g = lane >> 4, sub = lane & 15;
-    const int kslot = wave * FIN_KPW + g;  // keypoint slot in the workgroup
-    const int idx = bx * (NW * FIN_KPW) + kslot;
+    const int kslot = wave * ORB_KPW + g;  // keypoint slot in the workgroup
+    const int idx = bx * (NW * ORB_KPW) + kslot;
     // The keypoint's level and its index in the level from the levels'
     // inclusive count prefixes P_i (scalar: ocnt is read at uniform addresses,
     // the first eight counts by independent loads): the prefixes are
@@ -142,7 +89,7 @@ __global__ void __launch_bounds__(64 * NW) k_finalize_lds(const uint8_t* __restr
     const int k = (int)ku;
     const int total = acc < kp_cap ? acc : kp_cap;
     if (bx == 0 && threadIdx.x == 0) nkp[f] = total;
-    if (bx * (NW * FIN_KPW) >= total) return;  // uniform over the workgroup
+    if (bx * (NW * ORB_KPW) >= total) return;  // uniform over the workgroup
     const bool valid = idx < acc && idx < kp_cap;
     if (!valid) lvl = 0;
     const LevelDesc L = lv[lvl];
@@ -198,7 +145,7 @@ __global__ void __launch_bounds__(64 * NW) k_finalize_lds(const uint8_t* __restr
             }
         }
         {
-            uint32_t* d = P + ir * FL_IC_W + 3 * ic;
+            uint32_t* d = P + ir * ORB_IC_W + 3 * ic;
 #pragma unroll
             for (int j = 0; j < IC_STEPS; j++) {
                 if (glane && (j + 1 < IC_STEPS || ir == 0)) {
@@ -206,7 +153,7 @@ __global__ void __launch_bounds__(64 * NW) k_finalize_lds(const uint8_t* __restr
                     d[1] = v[j].y;
                     d[2] = v[j].z;
                 }
-                d += 5 * FL_IC_W;
+                d += 5 * ORB_IC_W;
             }
         }
     }
@@ -215,8 +162,8 @@ __global__ void __launch_bounds__(64 * NW) k_finalize_lds(const uint8_t* __restr
     {
         const bool has1 = sub < 15;
         const int v0 = sub - 15, v1 = has1 ? sub + 1 : 0;
-        const uint32_t* r0 = P + (v0 + 15) * FL_IC_W;
-        const uint32_t* r1 = P + (v1 + 15) * FL_IC_W;
+        const uint32_t* r0 = P + (v0 + 15) * ORB_IC_W;
+        const uint32_t* r1 = P + (v1 + 15) * ORB_IC_W;
         uint32_t w0[9], w1[9];
 #pragma unroll
         for (int i = 0; i < 9; i++) {
@@ -250,73 +197,43 @@ __global__ void __launch_bounds__(64 * NW) k_finalize_lds(const uint8_t* __restr
         m01 += __shfl_xor(m01, off);
     }
     const float angle = fast_atan2((float)m01, (float)m10);
-    const float factorPI = (float)(3.14159265358979323846 / 180.f);
-    const float ang = angle * factorPI;
-    double sd, cd;
-    sincos((double)ang, &sd, &cd);
-    const float a = (float)cd, b = (float)sd;
-    const f32x2 BA = {b, a}, AB = {a, b}, MAG = {RND_MAGIC, RND_MAGIC};
-    // staged byte of rotated offset (iy, ix): (iy + 18) * 40 + ix + 18 + sh2; the
-    // magic-rounded floats carry RND_BITS + offset in their bits
+    const float2 R = orb_rotation(angle);  // (cos, sin)
+    const f32x2 BA = {R.y, R.x}, AB = {R.x, R.y}, MAG = {ORB_RND_MAGIC, ORB_RND_MAGIC};
     __syncthreads();  // every IC disc read
     {
-        uint32_t* d = P + br * FL_BR_W + 2 * bc;
+        uint32_t* d = P + br * ORB_BR_W + 2 * bc;
 #pragma unroll
         for (int j = 0; j < BR_STEPS; j++) {
             if (glane && (j + 1 < BR_STEPS || br == 0)) *reinterpret_cast<uint2*>(d) = vbr[j];
-            d += 3 * FL_BR_W;
+            d += 3 * ORB_BR_W;
         }
     }
     __syncthreads();
     const uint8_t* PB = reinterpret_cast<const uint8_t*>(P);
-    // iy's low 24 bits are 0x400000 + dy (a 24-bit multiply: v_mad_u32_u24,
-    // full rate, where the 32-bit product took v_mad_u64_u32 until round 5)
-    const uint32_t cofs = (uint32_t)(18 * 4 * FL_BR_W + 18 + sh2) - 0x400000u * (uint32_t)(4 * FL_BR_W) - RND_BITS;  // mod 2^32
+    const uint32_t cofs = (uint32_t)(18 * 4 * ORB_BR_W + 18 + sh2) - 0x400000u * (uint32_t)(4 * ORB_BR_W) - ORB_RND_BITS;  // mod 2^32
     int tv0[16], tv1[16];
     uint32_t pat8[16];
 #pragma unroll
     for (int u = 0; u < 4; u++) {
-        const uint4 q = reinterpret_cast<const uint4*>(c_pat8)[sub * 4 + u];
+        const uint4 q = reinterpret_cast<const uint4*>(c_pat8.w)[sub * 4 + u];
         pat8[4 * u] = q.x, pat8[4 * u + 1] = q.y, pat8[4 * u + 2] = q.z, pat8[4 * u + 3] = q.w;
     }
 #pragma unroll
     for (int w = 0; w < 16; w++) {
         const uint32_t pw = pat8[w];
-        const float4 Pt = {(float)(int8_t)(pw & 0xff), (float)(int8_t)((pw >> 8) & 0xff),
-                           (float)(int8_t)((pw >> 16) & 0xff), (float)(int8_t)(pw >> 24)};
+        const float4 Pt = orb_test_points(pw);
         f32x2 q0 = (f32x2){Pt.x, Pt.x} * BA + (f32x2){Pt.y, -Pt.y} * AB;
         f32x2 q1 = (f32x2){Pt.z, Pt.z} * BA + (f32x2){Pt.w, -Pt.w} * AB;
         q0 = q0 + MAG;
         q1 = q1 + MAG;
-        const uint32_t o0 = __umul24(__float_as_uint(q0.x), (uint32_t)(4 * FL_BR_W)) + __float_as_uint(q0.y) + cofs;
-        const uint32_t o1 = __umul24(__float_as_uint(q1.x), (uint32_t)(4 * FL_BR_W)) + __float_as_uint(q1.y) + cofs;
+        const uint32_t o0 = __umul24(__float_as_uint(q0.x), (uint32_t)(4 * ORB_BR_W)) + __float_as_uint(q0.y) + cofs;
+        const uint32_t o1 = __umul24(__float_as_uint(q1.x), (uint32_t)(4 * ORB_BR_W)) + __float_as_uint(q1.y) + cofs;
         tv0[w] = PB[o0];
         tv1[w] = PB[o1];
     }
-    // all sixteen ballots first (scalar registers), then lane 0 stores them in
-    // one block: a store after each ballot was sixteen exec-mask branch
-    // blocks that every wave entered. The empty asm keeps the stores 64 bits
-    // wide, one v_mov_b64 each: merged into 128-bit stores they take two
-    // 32-bit moves per ballot
-    uint64_t bal[16];
-#pragma unroll
-    for (int w = 0; w < 16; w++) bal[w] = __ballot(tv0[w] < tv1[w]);
-    if (lane == 0) {
-#pragma unroll
-        for (int w = 0; w < 16; w++) {
-            s_bal[wave][w] = bal[w];
-            asm volatile("" ::: "memory");
-        }
-    }
-    __syncthreads();
-    const int o = idx;
-    if (valid && sub < 8) {
-        const uint32_t lo = (uint32_t)(s_bal[wave][2 * sub] >> (16 * g)) & 0xffffu;
-        const uint32_t hi = (uint32_t)(s_bal[wave][2 * sub + 1] >> (16 * g)) & 0xffffu;
-        reinterpret_cast<uint32_t*>(desc + ((size_t)f * kp_cap + o) * 32)[sub] = lo | (hi << 16);
-    }
+    orb_store_desc(tv0, tv1, s_bal, wave, lane, valid, desc, f, kp_cap, idx);
     if (valid && sub == 0) {
-        orb_kp* kp = kps + (size_t)f * kp_cap + o;
+        orb_kp* kp = kps + (size_t)f * kp_cap + idx;
         float px = (float)kx, py = (float)ky;
         if (lvl != 0) {
             px *= L.scale;
@@ -343,18 +260,6 @@ __global__ void __launch_bounds__(256) k_kp_geometry(const orb_kp* __restrict__ 
     const size_t o = (size_t)f * kp_cap + i;
     const float2 p = *reinterpret_cast<const float2*>(&kps[o].x);
     kp_geometry(p.x, p.y, cal, depth + (size_t)f * depth_stride, img_w, kun + o * 2, xyz + o * 3, ur + o);
-}
-
-void upload_finalize_constants() {
-    uint32_t pat8[256];
-    for (int sl = 0; sl < 16; sl++)
-        for (int w = 0; w < 16; w++) {
-            const int t = w * 16 + sl;
-            uint32_t v = 0;
-            for (int i = 0; i < 4; i++) v |= (uint32_t)(uint8_t)(int8_t)ODO_ORB_PATTERN[4 * t + i] << (8 * i);
-            pat8[sl * 16 + w] = v;
-        }
-    hipMemcpyToSymbol(HIP_SYMBOL(c_pat8), pat8, sizeof(pat8));
 }
 
 void launch_kp_geometry(hipStream_t st, const orb_kp* kps, const int* nkp, const uint16_t* depth, size_t depth_stride,

@@ -226,9 +226,6 @@ odo_ctx* odo_create(const odo_config* cfg, int device) {
         delete c;
         return nullptr;
     }
-    upload_extract_constants();
-    upload_adaptive_constants();
-    upload_adaptive_orb_constants();
     c->cal = frame_calib(cfg->calib);
     c->nev = 11;
     for (int i = 0; i < c->nev; i++) (void)c->make_event(&c->ev[i], hipEventDefault);

@@ -230,8 +230,6 @@ struct RansacCfg {
 };
 
 // ---- launch wrappers (defined next to their kernels)
-void upload_extract_constants();
-void upload_finalize_constants();
 void launch_kp_geometry(hipStream_t st, const orb_kp* kps, const int* nkp, const uint16_t* depth, size_t depth_stride,
                         int img_w, FrameCalib cal, float* kun, float* xyz, float* ur, int kp_cap, int nframes);
 void launch_gray(hipStream_t st, const uint8_t* bgr, uint8_t* pyr, int w, int h, int pitch, size_t in_stride,
@@ -573,7 +571,6 @@ struct CloudArgs {
 void launch_cloud_voxels(hipStream_t st, const CloudArgs& a);
 // the voxel starts and the centroids into out / counts; max_points: the largest n_points of a frame
 void launch_cloud_points(hipStream_t st, const CloudArgs& a, int max_points);
-void upload_adaptive_constants();
 void launch_adapt_smap(hipStream_t st, const uint8_t* pyr, size_t pyr_stride, int w, int h, int pitch, uint8_t* smap,
                        size_t smap_stride, int nframes);
 void launch_adapt_cand(hipStream_t st, const uint8_t* smap, size_t smap_stride, int pitch, const AdBand* bands,
@@ -594,7 +591,6 @@ void launch_adapt_finalize(hipStream_t st, const uint8_t* blur, size_t pyr_strid
                            int akp_stride, const int* nkp, float ca, float sb, const uint16_t* depth,
                            size_t depth_stride, int img_w, FrameCalib cal, orb_kp* kps, uint8_t* desc, float* kun,
                            float* xyz, float* ur, int kp_cap, int nframes);
-void upload_adaptive_orb_constants();
 void launch_oa_pyr(hipStream_t st, const uint8_t* pyr, size_t pyr_stride, int gpitch, const OaCell* cells, int ncells,
                    const OaImg* imgs, int buf0, int buf1, uint8_t* cpyr, size_t cp_stride, int nframes);
 size_t oa_scand_lds_bytes(int maxpitch);

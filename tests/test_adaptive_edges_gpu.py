@@ -135,6 +135,49 @@ def test_orb_inner_case(name, w, h, params, start):
                 nonempty=True)
 
 
+def windows_past_level_edges(frames, w, h):
+    """Per level edge (left, top, right, bottom): how many oracle keypoints
+    have an rBRIEF window, 18 px around the centre cvRound(pt / scale) of
+    their octave's level of the frame pyramid, that crosses it."""
+    lw, lh = np.zeros(8, np.int32), np.zeros(8, np.int32)
+    sc, q = np.zeros(8, np.float32), np.zeros(8, np.int32)
+    O.lib().oracle_orbcv_levels(w, h, O.ptr(lw), O.ptr(lh), O.ptr(sc), O.ptr(q))
+    hits = np.zeros(4, np.int64)
+    for f in frames:
+        k = f["kps"]
+        o = k["octave"]
+        inv = np.float32(1) / sc[o]
+        cx, cy = np.rint(k["x"] * inv).astype(np.int64), np.rint(k["y"] * inv).astype(np.int64)
+        hits += [np.sum(cx < 18), np.sum(cy < 18), np.sum(cx + 18 >= lw[o]), np.sum(cy + 18 >= lh[o])]
+    return hits
+
+
+def test_orb_inner_windows_leave_the_level():
+    """rBRIEF windows that cross each of the four edges of their level (the
+    byte-by-byte REFLECT_101 staging of k_oa_finalize), in workgroups that also
+    hold in-level keypoints and, at a frame's end, invalid slots.
+
+    orb_3x5_edge0's grid, overlap, totals and start thresholds with
+    retain_best off, on noise in 6 x 6 px blocks: white noise has FAST corners
+    on level 0 only, whose windows runByImageBorder(31) keeps inside; blocks
+    give the cell pyramids corners up to octave 4, and a cell at the frame's
+    border then puts a centre within 18 px of its level's edge. Seed chosen
+    with the oracle: 4 / 2 / 5 / 3 such keypoints, 245 and 301 per frame."""
+    pkg = load_pkg()
+    w, h, b = 320, 240, 6
+    rng = np.random.default_rng(3)
+    blocks = rng.integers(0, 256, (2, h // b, -(-w // b), 3), dtype=np.uint8)
+    bgr = np.ascontiguousarray(np.repeat(np.repeat(blocks, b, 1), b, 2)[:, :h, :w])
+    dep = rng.integers(2000, 20000, (2, h, w)).astype(np.uint16)
+    params = dict(grid_rows=3, grid_cols=5, edge_threshold=0, max_total_keypoints=450, cell_min=5, cell_max=40,
+                  retain_best=-1)
+    frames = check_batch(pkg, params, bgr, dep, np.linspace(3.0, 45.0, 15), "orb", 8, "orb_3x5_edge0_blocks",
+                         nonempty=True)
+    hits = windows_past_level_edges(frames, w, h)
+    assert hits.min() >= 1, f"windows past the (left, top, right, bottom) level edges: {hits}"
+    assert any(len(f["kps"]) % 8 for f in frames), "no frame ends inside a finalize workgroup"
+
+
 # ---------------------------------------------------------------- refusals
 def orb_min_quota():
     lw, lh = np.zeros(8, np.int32), np.zeros(8, np.int32)

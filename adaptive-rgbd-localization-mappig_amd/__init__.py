@@ -21,7 +21,9 @@ from ._abi import (DETECTOR_ADAPTIVE_FAST, DETECTOR_ADAPTIVE_ORB, DETECTOR_ORB_S
                    BA_EDGE_DTYPE, BA_NOTHING, BA_RAN, BaParams, BaResult,
                    FUSE_BAD, FUSE_BEHIND, FUSE_CAND_DTYPE, FUSE_CANDS, FUSE_KF_DTYPE, FUSE_NULL, FUSE_OUTSIDE,
                    CLOUD_DTYPE, CLOUD_INFO_DTYPE, CLOUD_OK, CLOUD_UNFILTERED, ERR_CAPACITY, SOR_INFO_DTYPE,
-                   SOR_OK, SOR_SKIPPED, SOR_MAX_K)
+                   SOR_OK, SOR_SKIPPED, SOR_MAX_K,
+                   ICP_RESULT_DTYPE, ICP_GATE_AS_WRITTEN, ICP_GATE_PLANE, ICP_OK, ICP_NO_MODEL, ICP_SHORT_TEMPLATE,
+                   ICP_SINGULAR, IcpParams)
 
 __all__ = ["Odometry", "HostFrames", "PinnedResults", "default_config", "load", "KP_DTYPE", "DMATCH_DTYPE", "PAIR_DTYPE", "rng_stream",
            "kabsch", "Calib", "OrbParams", "RansacParams", "Config", "AdaptiveParams", "DETECTOR_ORB_SLAM2",
@@ -32,7 +34,8 @@ __all__ = ["Odometry", "HostFrames", "PinnedResults", "default_config", "load", 
            "LM_BAD", "LM_SEEN", "LM_HAS_OBS", "BA_EDGE_DTYPE", "BaParams", "BaResult", "BA_RAN", "BA_NOTHING",
            "default_ba_params", "fuse_best", "FUSE_KF_DTYPE", "FUSE_CAND_DTYPE", "FUSE_CANDS", "FUSE_NULL", "FUSE_BAD",
            "FUSE_BEHIND", "FUSE_OUTSIDE", "CLOUD_DTYPE", "CLOUD_INFO_DTYPE", "CLOUD_OK", "CLOUD_UNFILTERED",
-           "SOR_INFO_DTYPE", "SOR_OK", "SOR_SKIPPED", "SOR_MAX_K"]
+           "SOR_INFO_DTYPE", "SOR_OK", "SOR_SKIPPED", "SOR_MAX_K", "ICP_RESULT_DTYPE", "ICP_GATE_AS_WRITTEN",
+           "ICP_GATE_PLANE", "ICP_OK", "ICP_NO_MODEL", "ICP_SHORT_TEMPLATE", "ICP_SINGULAR", "IcpParams", "icp_params"]
 
 
 def default_config(width=640, height=480, max_batch=1, nfeatures=1000, iterations=200, seed=0x5EED0000,
@@ -790,11 +793,73 @@ class Odometry:
         check(self.lib.odo_gicp_dense_fitness(self.h, ptr(pr), P, ptr(M), ptr(score)))
         return score[:P]
 
+    def icp_normals(self, clouds, num_neighbors: int = 10, cell: float = 0.0):
+        """odo_icp_normals: libicp's computeNormals of a list of n x 3 clouds in one
+        launch chain. Returns a list of n x 3 float32 arrays (zeros for a cloud
+        under 5 points)."""
+        offs = np.zeros(len(clouds) + 1, np.int32)
+        offs[1:] = np.cumsum([len(c) for c in clouds])
+        P = np.ascontiguousarray(np.concatenate([np.asarray(c, np.float32).reshape(-1, 3) for c in clouds])
+                                 if clouds else np.zeros((0, 3), np.float32))
+        nrm = np.full((max(int(offs[-1]), 1), 3), np.nan, np.float32)
+        check(self.lib.odo_icp_normals(self.h, ptr(P), ptr(offs), len(clouds), num_neighbors, cell, ptr(nrm)))
+        return [nrm[offs[k]:offs[k + 1]] for k in range(len(clouds))]
+
+    def icp_plane_batch(self, pairs, params=None, cell: float = 0.0):
+        """libicp's IcpPointToPlane(model).fit(template, R, t, indist)
+        (odo_icp_plane_batch) for a list of (template n x 3, model m x 3, guess 4x4
+        or None). params: an IcpParams (icp_params()), None = libicp's defaults.
+        Returns the ICP_RESULT_DTYPE records, one per pair."""
+        P = len(pairs)
+        to = np.zeros(P + 1, np.int32)
+        mo = np.zeros(P + 1, np.int32)
+        to[1:] = np.cumsum([len(t) for t, _, _ in pairs])
+        mo[1:] = np.cumsum([len(m) for _, m, _ in pairs])
+        cat = lambda xs: np.ascontiguousarray(np.concatenate([np.asarray(x, np.float32).reshape(-1, 3) for x in xs])
+                                              if xs else np.zeros((0, 3), np.float32))
+        tmpl, model = cat([t for t, _, _ in pairs]), cat([m for _, m, _ in pairs])
+        g = np.ascontiguousarray(np.stack([np.eye(4, dtype=np.float32) if q is None else np.asarray(q, np.float32)
+                                           for _, _, q in pairs]) if P else np.zeros((1, 4, 4), np.float32))
+        prm = icp_params() if params is None else params
+        out = np.zeros(max(P, 1), ICP_RESULT_DTYPE)
+        check(self.lib.odo_icp_plane_batch(self.h, ptr(tmpl), ptr(to), ptr(model), ptr(mo), ptr(g), P, C.byref(prm), cell,
+                                           ptr(out)))
+        return out[:P]
+
+    def icp_plane_dense(self, pairs, guesses=None, params=None):
+        """odo_icp_plane_dense: the same for a list of (template frame, model
+        frame) of the last dense-cloud call, on the clouds where they lie in HBM.
+        guesses: a list of 4x4 or None per pair, or None."""
+        P = len(pairs)
+        pr = np.ascontiguousarray(np.asarray(pairs, np.int32).reshape(-1, 2) if P else np.zeros((1, 2), np.int32))
+        g = None
+        if guesses is not None and P:
+            g = np.ascontiguousarray(np.stack([np.eye(4, dtype=np.float32) if q is None else np.asarray(q, np.float32)
+                                               for q in guesses]))
+            assert g.shape == (P, 4, 4)
+        prm = icp_params() if params is None else params
+        out = np.zeros(max(P, 1), ICP_RESULT_DTYPE)
+        check(self.lib.odo_icp_plane_dense(self.h, ptr(pr), P, None if g is None else ptr(g), C.byref(prm), ptr(out)))
+        return out[:P]
+
     def timings(self):
         ms = np.zeros(16, np.float32)
         names = (C.c_char_p * 16)()
         n = self.lib.odo_last_timings(self.h, ptr(ms), 16, C.cast(names, C.c_void_p))
         return {names[i].decode(): float(ms[i]) for i in range(n)}
+
+
+def icp_params(num_neighbors: int = None, max_iterations: int = None, min_delta: float = None, indist: float = None,
+               gate: int = None) -> "IcpParams":
+    """odo_default_icp_params (libicp's 10, 200, 1e-4, -1, the gate as written)
+    with the given fields replaced."""
+    p = IcpParams()
+    load().odo_default_icp_params(C.byref(p))
+    for k, v in (("num_neighbors", num_neighbors), ("max_iterations", max_iterations), ("min_delta", min_delta),
+                 ("indist", indist), ("gate", gate)):
+        if v is not None:
+            setattr(p, k, v)
+    return p
 
 
 def rng_stream(seed: int, n: int) -> np.ndarray:

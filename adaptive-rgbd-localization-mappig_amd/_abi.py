@@ -176,6 +176,15 @@ CLOUD_INFO_DTYPE = np.dtype([("status", "<i4"), ("n_valid", "<i4"), ("n_points",
                              ("div_b", "<i4", 3), ("min_p", "<f4", 3), ("max_p", "<f4", 3)])  # odo_cloud_info
 SOR_INFO_DTYPE = np.dtype([("status", "<i4"), ("n_in", "<i4"), ("n_out", "<i4"), ("pad", "<i4"), ("mean", "<f8"),
                            ("stddev", "<f8"), ("threshold", "<f8")])  # odo_sor_info
+ICP_RESULT_DTYPE = np.dtype([("T", "<f4", 16), ("residual", "<f8"), ("delta", "<f4"), ("iterations", "<i4"),
+                             ("n_active", "<i4"), ("status", "<i4")])  # odo_icp_result
+ICP_GATE_AS_WRITTEN, ICP_GATE_PLANE = 0, 1  # include/odo_types.h ODO_ICP_GATE_*
+ICP_OK, ICP_NO_MODEL, ICP_SHORT_TEMPLATE, ICP_SINGULAR = 0, 1, 2, 3  # ODO_ICP_*
+
+
+class IcpParams(C.Structure):  # odo_icp_params
+    _fields_ = [("num_neighbors", C.c_int32), ("max_iterations", C.c_int32), ("gate", C.c_int32), ("pad", C.c_int32),
+                ("min_delta", C.c_double), ("indist", C.c_double)]
 
 # Every symbol include/odo.h declares, with its ctypes signature.
 SIGNATURES = {
@@ -252,6 +261,10 @@ SIGNATURES = {
     "odo_cloud_sor_batch": (C.c_int, [P, P, P, C.c_int, C.c_int, C.c_double, C.c_float, P, P, P]),
     "odo_gicp_grid_fitness": (C.c_int, [P, P, P, P, P, P, C.c_int, C.c_float, P, P]),
     "odo_gicp_dense_fitness": (C.c_int, [P, P, C.c_int, P, P]),
+    "odo_default_icp_params": (None, [P]),
+    "odo_icp_normals": (C.c_int, [P, P, P, C.c_int, C.c_int, C.c_float, P]),
+    "odo_icp_plane_batch": (C.c_int, [P, P, P, P, P, P, C.c_int, P, C.c_float, P]),
+    "odo_icp_plane_dense": (C.c_int, [P, P, C.c_int, P, P, P]),
     "odo_default_ba_params": (None, [P]),
     "odo_local_ba": (C.c_int, [P, P, P, C.c_int, P, C.c_int, P, C.c_int, P, P, P, P]),
     "odo_ransac_hyps": (C.c_int, [P, P, C.c_int, P, C.c_int, P, C.c_int, P, P, P, C.c_int, C.c_int, P, P]),

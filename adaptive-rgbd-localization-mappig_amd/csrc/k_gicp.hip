@@ -43,6 +43,7 @@
 #include <cfloat>
 #include <cstring>
 
+#include "odo_gg_walk.h"
 #include "odo_internal.h"
 #include "odo_linalg.h"
 #include "odo_wave.h"
@@ -56,17 +57,6 @@ constexpr int GI_THREADS = 256;  // the ICP / BFGS workgroup: 4 waves share ever
 constexpr int GI_WAVES = GI_THREADS / GI_LANES;
 constexpr int GI_NV = 12;        // values reduced per gradient evaluation
 constexpr int GI_STAGE = 4096;   // clouds up to this many points are staged in LDS (48 KB)
-
-__device__ __forceinline__ float dist2f(const float* a, const float* b) {
-    float r = 0.f, d;
-    d = a[0] - b[0];
-    r += d * d;
-    d = a[1] - b[1];
-    r += d * d;
-    d = a[2] - b[2];
-    r += d * d;
-    return r;
-}
 
 // computeCovariances from the ordered neighbour list nn[20] of point q on:
 // mean and covariance in double, eigenvalues replaced by (1, 1, eps). One piece
@@ -816,15 +806,6 @@ __global__ __launch_bounds__(GI_THREADS) void k_gicp(const float* __restrict__ s
 // (DESIGN §4 "Dense GICP"; GgCloud in odo_internal.h)
 constexpr int GG_CHUNK = 4096;  // cells per scan workgroup, points per bounds workgroup
 
-__device__ __forceinline__ void gg_cell3(const GgCloud& g, const float* p, int* c) {
-    const int dim[3] = {g.gx, g.gy, g.gz};
-#pragma unroll
-    for (int a = 0; a < 3; a++) {
-        const float t = (p[a] - g.mn[a]) * g.inv;
-        c[a] = (int)fminf(fmaxf(floorf(t), 0.f), (float)(dim[a] - 1));  // outside (a query): clipped
-    }
-}
-
 // grid (point blocks, clouds)
 __global__ __launch_bounds__(256) void k_gg_pack(const float* __restrict__ src, int stride,
                                                  const int* __restrict__ row0, const int* __restrict__ offs,
@@ -940,45 +921,7 @@ __global__ __launch_bounds__(256) void k_gg_scatter(const float* __restrict__ P,
     sorted[pos] = make_float4(P[3 * row], P[3 * row + 1], P[3 * row + 2], __int_as_float(i));
 }
 
-// The ring walk, once: every point of the cells at Chebyshev distance 0, 1, 2
-// ... from cell c goes to v.visit(row of `sorted`), and after ring r the walk
-// stops when the k-th distance the visitor holds (v.kth(), +inf while it holds
-// fewer) is STRICTLY below what any unseen point can have (gg_ring_bound), or
-// when the rings have covered the grid. c is gg_cell3 of the query. For a query
-// q outside the cloud's bounds that is also the cell of q', q clamped per axis
-// into the bounds (the computed t is monotone in the coordinate and the
-// bounds' own cells are 0 and dim - 1), and |p_a - q_a| >= |p_a - q'_a| for
-// every point p of the cloud and every axis a, so the bound that holds for q'
-// holds for any finite q (DESIGN §4 "SOR and fitness").
-template <class V>
-__device__ __forceinline__ void gg_walk(const GgCloud& g, const int* __restrict__ cs,
-                                        const float4* __restrict__ sorted, const int* c, V& v) {
-    const int rmax = max(max(max(c[0], g.gx - 1 - c[0]), max(c[1], g.gy - 1 - c[1])), max(c[2], g.gz - 1 - c[2]));
-    for (int r = 0;; r++) {
-        const int z0 = max(c[2] - r, 0), z1 = min(c[2] + r, g.gz - 1);
-        const int y0 = max(c[1] - r, 0), y1 = min(c[1] + r, g.gy - 1);
-        const int x0 = max(c[0] - r, 0), x1 = min(c[0] + r, g.gx - 1);
-        for (int z = z0; z <= z1; z++)
-            for (int y = y0; y <= y1; y++) {
-                const int row = (z * g.gy + y) * g.gx;
-                // a row on the shell's z or y faces is one run of cells, any
-                // other row has the shell's two x faces
-                const bool full = abs(z - c[2]) == r || abs(y - c[1]) == r;
-                for (int k = 0; k < 2; k++) {
-                    int xa = x0, xb = x1;
-                    if (full) {
-                        if (k) break;
-                    } else {
-                        xa = xb = k ? c[0] + r : c[0] - r;
-                        if (xa < 0 || xa > g.gx - 1) continue;
-                    }
-                    const int e = cs[row + xb + 1];
-                    for (int i = cs[row + xa]; i < e; i++) v.visit(sorted[i]);
-                }
-            }
-        if (r >= rmax || (double)v.kth() < gg_ring_bound(g.w, g.slack, r)) break;
-    }
-}
+// (the ring walk gg_walk: odo_gg_walk.h)
 
 // the covariance neighbours: the top 20 by (distance, index) in registers
 // (an unrolled insertion list; as cov_point: +inf padding, whose index 0 no

@@ -407,6 +407,115 @@ int run_fitness(odo_ctx* c, const Source& src, const std::vector<int32_t>& offs,
     return ODO_OK;
 }
 
+// The ICP cell rule: the same table budget as SOR's for num_neighbors
+// neighbours; the one-neighbour sweeps share the grid. A speed choice.
+double icp_cells_per_point(int num_neighbors) { return std::min(16.0, 160.0 / num_neighbors); }
+
+int check_icp_plane_params(const odo_icp_params* p, const float* guesses, int nprob, const char* who) {
+    if (!p) return fail(ODO_ERR_ARG, std::string(who) + ": null params");
+    if (p->num_neighbors < 3) return fail(ODO_ERR_ARG, std::string(who) + ": num_neighbors < 3");
+    if (p->max_iterations < 0) return fail(ODO_ERR_ARG, std::string(who) + ": max_iterations < 0");
+    if (!std::isfinite(p->min_delta) || !std::isfinite(p->indist))
+        return fail(ODO_ERR_ARG, std::string(who) + ": min_delta and indist must be finite");
+    if (p->gate != ODO_ICP_GATE_AS_WRITTEN && p->gate != ODO_ICP_GATE_PLANE)
+        return fail(ODO_ERR_ARG, std::string(who) + ": unknown gate");
+    if (guesses && !all_finite(guesses, 16 * (size_t)nprob)) return fail(ODO_ERR_ARG, std::string(who) + ": a guess is not finite");
+    if (p->num_neighbors > ICP_MAX_K) return fail(ODO_ERR_CAPACITY, std::string(who) + ": num_neighbors above 32");
+    return ODO_OK;
+}
+
+// IcpPointToPlane. pairs (s = template, t = model) / guesses / out (nprob), or
+// normals (of every cloud, in point order), not both.
+int run_icp(odo_ctx* c, const Source& src, const std::vector<int32_t>& offs, std::vector<GgPair>& pairs,
+            const float* guesses, const odo_icp_params& prm, float cell, const char* who, odo_icp_result* out,
+            float* normals) {
+    const int ncl = (int)offs.size() - 1, nprob = (int)pairs.size();
+    const size_t N = (size_t)offs[ncl], NC = (size_t)ncl, NP = (size_t)nprob;
+    size_t W;
+    int e;
+    if ((e = pair_rows(offs, pairs, who, &W))) return e;
+    int max_ns = 0;
+    for (auto& p : pairs) max_ns = std::max(max_ns, offs[p.s + 1] - offs[p.s]);
+    std::vector<int32_t> need(NC, normals ? 1 : 0);
+    for (auto& p : pairs) need[p.t] = 1;
+    Pack pk;
+    const GridSections gs(pk, N, NC);
+    const size_t o_need = pk.add(NC * 4), o_nrm = pk.add(N * 12), o_pairs = pk.add(NP * sizeof(GgPair)),
+                 o_state = pk.add(NP * sizeof(IcpState)), o_left = pk.add(4), o_rows = pk.add(W * 32);
+    Grids G;
+    if ((e = build_grids(c, src, offs, gs, pk.off, cell, 0.0, icp_cells_per_point(prm.num_neighbors), who, &G))) return e;
+    uint8_t* d = G.d;
+    hipStream_t st = c->stream;
+    float* dnrm = (float*)(d + o_nrm);
+    if (ncl) HIPCHK(hipMemcpyAsync(d + o_need, need.data(), NC * 4, hipMemcpyHostToDevice, st));
+    if (N) HIPCHK(hipMemsetAsync(dnrm, 0, N * 12, st));  // clouds under 5 points: zeros
+    launch_icp_normals(st, G.dP, G.dcl, (const int*)(d + o_need), ncl, G.max_n, G.cstart, G.sorted, prm.num_neighbors,
+                       dnrm);
+    HIPCHK(hipGetLastError());
+    if (normals) {
+        if (N) HIPCHK(hipMemcpyAsync(normals, dnrm, N * 12, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        return ODO_OK;
+    }
+    // fit's exits (icp.cpp:43-52) and fitIterate's start
+    std::vector<IcpState> hs(NP);
+    int left = 0;
+    for (size_t p = 0; p < NP; p++) {
+        IcpState& s = hs[p];
+        memset(&s, 0, sizeof s);
+        for (int i = 0; i < 3; i++) {
+            for (int j = 0; j < 3; j++) s.R[3 * i + j] = guesses ? guesses[16 * p + 4 * i + j] : (i == j ? 1.f : 0.f);
+            s.t[i] = guesses ? guesses[16 * p + 4 * i + 3] : 0.f;
+        }
+        s.delta = 1000.f;
+        s.indist = prm.indist;
+        const int nm = offs[pairs[p].t + 1] - offs[pairs[p].t], nt = offs[pairs[p].s + 1] - offs[pairs[p].s];
+        s.status = nm < 5 ? ODO_ICP_NO_MODEL : nt < 5 ? ODO_ICP_SHORT_TEMPLATE : ODO_ICP_OK;
+        s.done = s.status != ODO_ICP_OK || !(0 < prm.max_iterations && 1000.0 > prm.min_delta);
+        left += !s.done;
+    }
+    IcpState* dstate = (IcpState*)(d + o_state);
+    int* dleft = (int*)(d + o_left);
+    float* drows = (float*)(d + o_rows);
+    const GgPair* dpairs = (const GgPair*)(d + o_pairs);
+    HIPCHK(hipMemcpyAsync(dstate, hs.data(), NP * sizeof(IcpState), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(dleft, &left, 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d + o_pairs, pairs.data(), NP * sizeof(GgPair), hipMemcpyHostToDevice, st));
+    // rounds of sweep + step with nothing read back; every 8th round the
+    // counter of unfinished pairs, to stop early
+    for (int r = 0; r < prm.max_iterations && left > 0; r++) {
+        launch_icp_sweep(st, G.dcl, dpairs, nprob, max_ns, G.cstart, G.sorted, dnrm, dstate, prm.gate, prm.indist, 0,
+                         drows);
+        launch_icp_step(st, G.dcl, dpairs, nprob, drows, dstate, prm.max_iterations, prm.min_delta, 0, dleft);
+        if (r % 8 == 7) {
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipMemcpyAsync(&left, dleft, 4, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipStreamSynchronize(st));
+        }
+    }
+    launch_icp_sweep(st, G.dcl, dpairs, nprob, max_ns, G.cstart, G.sorted, dnrm, dstate, prm.gate, prm.indist, 1, drows);
+    launch_icp_step(st, G.dcl, dpairs, nprob, drows, dstate, prm.max_iterations, prm.min_delta, 1, dleft);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(hs.data(), dstate, NP * sizeof(IcpState), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    for (size_t p = 0; p < NP; p++) {
+        const IcpState& s = hs[p];
+        odo_icp_result& o = out[p];
+        for (int i = 0; i < 3; i++) {
+            for (int j = 0; j < 3; j++) o.T[4 * i + j] = s.R[3 * i + j];
+            o.T[4 * i + 3] = s.t[i];
+        }
+        o.T[12] = o.T[13] = o.T[14] = 0.f;
+        o.T[15] = 1.f;
+        o.residual = s.residual;
+        o.delta = s.delta;
+        o.iterations = s.iter;
+        o.n_active = s.n_active;
+        o.status = s.status;
+    }
+    return ODO_OK;
+}
+
 }  // namespace
 }  // namespace odo
 
@@ -622,6 +731,114 @@ int odo_gicp_dense_fitness(odo_ctx* c, const int32_t* pairs, int nprob, const fl
         (k & 1 ? pr[k / 2].t : pr[k / 2].s) = cloud_of[f];
     }
     return run_fitness(c, s, offs, pr, T, 0.f, who, score, nullptr);
+}
+
+void odo_default_icp_params(odo_icp_params* p) {
+    if (!p) return;
+    p->num_neighbors = 10;  // icpPointToPlane.h
+    p->max_iterations = 200;  // icp.cpp:7-8
+    p->gate = ODO_ICP_GATE_AS_WRITTEN;
+    p->pad = 0;
+    p->min_delta = 1e-4;
+    p->indist = -1;  // icp.h: fit's default
+}
+
+int odo_icp_normals(odo_ctx* c, const float* P, const int32_t* offs, int ncl, int num_neighbors, float cell,
+                    float* normals) {
+    const char* who = "icp_normals";
+    if (!c || ncl < 0 || !offs) return fail(ODO_ERR_ARG, "bad icp_normals args");
+    if (num_neighbors < 3) return fail(ODO_ERR_ARG, "icp_normals: num_neighbors < 3");
+    if (!(cell >= 0) || !std::isfinite(cell)) return fail(ODO_ERR_ARG, "icp_normals: cell must be finite and >= 0");
+    if (num_neighbors > odo::ICP_MAX_K) return fail(ODO_ERR_CAPACITY, "icp_normals: num_neighbors above 32");
+    if (ncl == 0) return ODO_OK;
+    if (ncl > 65535) return fail(ODO_ERR_CAPACITY, "icp_normals: more than 65535 clouds per call");
+    int e;
+    if ((e = check_offs(offs, ncl, who))) return e;
+    const size_t N = (size_t)offs[ncl];
+    if (N == 0) return ODO_OK;
+    if (!P || !normals) return fail(ODO_ERR_ARG, "bad icp_normals args");
+    if (N > (size_t)INT32_MAX / 4) return fail(ODO_ERR_CAPACITY, "icp_normals: more than 2^29 points per call");
+    if (!all_finite(P, 3 * N)) return fail(ODO_ERR_ARG, "icp_normals: a coordinate is not finite");
+    if ((e = sync_all(c))) return e;
+    std::vector<int32_t> o(offs, offs + ncl + 1);
+    std::vector<GgPair> none;
+    Source s;
+    s.host[0] = P;
+    s.host_rows[0] = N;
+    odo_icp_params prm;
+    odo_default_icp_params(&prm);
+    prm.num_neighbors = num_neighbors;
+    return run_icp(c, s, o, none, nullptr, prm, cell, who, nullptr, normals);
+}
+
+int odo_icp_plane_batch(odo_ctx* c, const float* tmpl, const int32_t* toffs, const float* model, const int32_t* moffs,
+                        const float* guesses, int nprob, const odo_icp_params* params, float cell,
+                        odo_icp_result* out) {
+    const char* who = "icp_plane_batch";
+    if (!c || nprob < 0 || !toffs || !moffs || (nprob && !out)) return fail(ODO_ERR_ARG, "bad icp_plane_batch args");
+    int e;
+    if ((e = check_icp_plane_params(params, guesses, nprob, who))) return e;
+    if (!(cell >= 0) || !std::isfinite(cell)) return fail(ODO_ERR_ARG, "icp_plane_batch: cell must be finite and >= 0");
+    if (nprob == 0) return ODO_OK;
+    if (nprob > 32767) return fail(ODO_ERR_CAPACITY, "icp_plane_batch: more than 32767 pairs per call");
+    if ((e = check_offs(toffs, nprob, who)) || (e = check_offs(moffs, nprob, who))) return e;
+    const size_t S = (size_t)toffs[nprob], T = (size_t)moffs[nprob];
+    if ((S && !tmpl) || (T && !model)) return fail(ODO_ERR_ARG, "bad icp_plane_batch args");
+    if (S + T > (size_t)INT32_MAX / 4) return fail(ODO_ERR_CAPACITY, "icp_plane_batch: more than 2^29 points per call");
+    if (!all_finite(tmpl, 3 * S) || !all_finite(model, 3 * T))
+        return fail(ODO_ERR_ARG, "icp_plane_batch: a coordinate is not finite");
+    if ((e = sync_all(c))) return e;
+    // clouds: the templates, then the models
+    std::vector<int32_t> offs(2 * (size_t)nprob + 1);
+    std::vector<GgPair> pairs((size_t)nprob);
+    for (int p = 0; p <= nprob; p++) offs[p] = toffs[p];
+    for (int p = 1; p <= nprob; p++) offs[(size_t)nprob + p] = (int32_t)(S + (size_t)moffs[p]);
+    for (int p = 0; p < nprob; p++) pairs[p] = GgPair{p, nprob + p, 0};
+    Source s;
+    s.host[0] = tmpl;
+    s.host_rows[0] = S;
+    s.host[1] = model;
+    s.host_rows[1] = T;
+    return run_icp(c, s, offs, pairs, guesses, *params, cell, who, out, nullptr);
+}
+
+int odo_icp_plane_dense(odo_ctx* c, const int32_t* pairs, int nprob, const float* guesses,
+                        const odo_icp_params* params, odo_icp_result* out) {
+    const char* who = "icp_plane_dense";
+    if (!c) return fail(ODO_ERR_ARG, "icp_plane_dense: null ctx");
+    if (c->cloud_n < 0) return fail(ODO_ERR_STATE, "icp_plane_dense: no dense-cloud call yet");
+    if (nprob < 0 || (nprob && (!pairs || !out))) return fail(ODO_ERR_ARG, "bad icp_plane_dense args");
+    int e;
+    if ((e = check_icp_plane_params(params, guesses, nprob, who))) return e;
+    for (int k = 0; k < 2 * nprob; k++)
+        if (pairs[k] < 0 || pairs[k] >= c->cloud_n)
+            return fail(ODO_ERR_ARG, "icp_plane_dense: frame outside the last dense-cloud call");
+    if (nprob == 0) return ODO_OK;
+    if (nprob > 65535) return fail(ODO_ERR_CAPACITY, "icp_plane_dense: more than 65535 pairs per call");
+    if (c->cloud_n > 65535) return fail(ODO_ERR_CAPACITY, "icp_plane_dense: more than 65535 frames in the dense-cloud call");
+    if ((e = sync_all(c))) return e;
+    // the distinct frames, in the order they are named: one grid each, normals
+    // for those named as a model
+    std::vector<int> cloud_of((size_t)c->cloud_n, -1);
+    std::vector<int32_t> offs(1, 0);
+    std::vector<GgPair> pr((size_t)nprob);
+    Source s;
+    s.dev = (const float*)c->cloud_out.p;
+    s.stride = (int)(sizeof(odo_cloud_point) / 4);
+    for (int k = 0; k < 2 * nprob; k++) {
+        const int f = pairs[k];
+        if (cloud_of[f] < 0) {
+            if (c->cloud_np[f] > GG_MAX_POINTS)
+                return fail(ODO_ERR_CAPACITY, "icp_plane_dense: more than 1048576 points in a cloud");
+            if ((size_t)offs.back() + (size_t)c->cloud_np[f] > (size_t)INT32_MAX / 4)
+                return fail(ODO_ERR_CAPACITY, "icp_plane_dense: more than 2^29 points per call");
+            cloud_of[f] = (int)offs.size() - 1;
+            s.row0.push_back(c->cloud_off[f]);
+            offs.push_back(offs.back() + c->cloud_np[f]);
+        }
+        (k & 1 ? pr[k / 2].t : pr[k / 2].s) = cloud_of[f];
+    }
+    return run_icp(c, s, offs, pr, guesses, *params, 0.f, who, out, nullptr);
 }
 
 }  // extern "C"

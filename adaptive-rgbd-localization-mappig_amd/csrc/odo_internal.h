@@ -437,6 +437,31 @@ void launch_sor_pack(hipStream_t st, const GgCloud* cl, int ncl, int max_n, cons
 // over the whole target; score[pair] = their mean, DBL_MAX for an empty side
 void launch_gg_fitness(hipStream_t st, const GgCloud* cl, const GgPair* pairs, int nprob, int max_ns,
                        const int* cstart, const float4* sorted, const float* T, float* nn, double* score);
+// libicp's IcpPointToPlane over the same grids (k_icp.hip; DESIGN §4
+// "Point-to-plane ICP"). One record per pair, kept on the device between the
+// rounds of sweep + step:
+constexpr int ICP_MAX_K = 32;  // num_neighbors: 8 bytes per neighbour and lane of LDS
+struct IcpState {
+    float R[9], t[3];
+    float delta;
+    int iter, n_active, status, done, pad;
+    double indist, residual;
+};
+// computeNormals of every cloud k with need[k] != 0 and at least 5 points:
+// normals 3 floats per point, in point order (preset by the caller)
+void launch_icp_normals(hipStream_t st, const float* P, const GgCloud* cl, const int* need, int ncl, int max_n,
+                        const int* cstart, const float4* sorted, int num_neighbors, float* normals);
+// one search per template point at the pair's R, t: the gate and the row of
+// [A | b] into rows (8 words per point at the pair's `work`, point order);
+// residual != 0: getResidual's term of the last active set instead
+void launch_icp_sweep(hipStream_t st, const GgCloud* cl, const GgPair* pairs, int nprob, int max_ns,
+                      const int* cstart, const float4* sorted, const float* normals, const IcpState* state, int gate,
+                      double indist, int residual, float* rows);
+// fitStep's solve and composition per pair from its rows, the loop test and
+// the done latch (*unfinished counts the pairs still running); residual != 0:
+// the mean of the residual terms
+void launch_icp_step(hipStream_t st, const GgCloud* cl, const GgPair* pairs, int nprob, const float* rows,
+                     IcpState* state, int max_iterations, double min_delta, int residual, int* unfinished);
 // Batched ADAPTIVE_RICP / RANSAC back-ends (k_ricp.hip), on the pair stream
 // after launch_ransac. The branch rule's constants (odometry.cpp:52-53):
 struct RicpCfg {

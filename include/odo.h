@@ -765,6 +765,83 @@ int odo_gicp_grid_fitness(odo_ctx* ctx, const float* src, const int32_t* soffs, 
  * odo_gicp_dense. */
 int odo_gicp_dense_fitness(odo_ctx* ctx, const int32_t* pairs, int nprob, const float* T, double* score);
 
+/* ---- Point-to-plane ICP: libicp's IcpPointToPlane, batched ----
+ * Odometry/icp/ (icp.cpp, icpPointToPlane.cpp, matrix.cpp), dimension 3, as
+ * Tests/IcpPointToPlane.cpp:81-119 runs it on RANSAC's inlier clouds, over the
+ * grids of odo_gicp_grid_* (DESIGN §4 "Point-to-plane ICP"). The model is the
+ * target (the cloud with the normals), the template is moved: model = R *
+ * template + t. R, t are floats between iterations (matrix.h's FLOAT).
+ *   normals   of model point i: its num_neighbors nearest model points, itself
+ *           included, ascending by (d2, index) with d2 the float squared
+ *           distance of the GICP searches; all of them when the model has fewer;
+ *           mu (running float sums in that order, / (float)k), Q = P - mu, H = Q^T
+ *           Q (running float sums in that order); the eigenvector of H's
+ *           smallest eigenvalue from a double Jacobi SVD of (double)H, rounded
+ *           to float, then Matrix::svd's sign rule (matrix.cpp:853-867), which for
+ *           a symmetric H reads: negated when two or three components are
+ *           negative. An exactly zero smallest singular value (an exact plane)
+ *           is signed the same way.
+ *   loop      delta = 1000; while (iterations < max_iterations && delta >
+ *           min_delta): with indist > 0 first indist = max(indist * 0.9, 0.05)
+ *           and the active set = getInliers, else every point is active; delta
+ *           = fitStep.
+ *   search    s = R * T + t in double from the floats; the query is (float)s; its
+ *           nearest model point d by (d2, index), equal distances to the lower
+ *           model index (the reference's kd-tree order is unknown), no distance
+ *           cap; one search per iteration serves getInliers and fitStep.
+ *   gate      ODO_ICP_GATE_AS_WRITTEN: abs((sx - dx) * nx + (sy - dy) * ny + (sz -
+ *           dz)) * nz < indist, the reference's expression (a matched normal
+ *           with nz <= 0 is always active); ODO_ICP_GATE_PLANE: abs(n . (s - d))
+ *           < indist. s is the unrounded double here.
+ *   fitStep   per active point, s the float query read back: the row [nz * sy -
+ *           ny * sz, nx * sz - nz * sx, ny * sx - nx * sy, nx, ny, nz] and b = n
+ *           . d - n . s in double, stored as floats. A^T A and A^T b are summed in
+ *           double in a fixed order of the device's own (bit-identical run to
+ *           run, independent of the other pairs of the call) and rounded to
+ *           float once; the reference's running float sums differ within the
+ *           tolerance DESIGN §4 records. Then on floats in the reference's
+ *           order: Gauss-Jordan with full pivoting (a pivot below 1e-20 fails:
+ *           delta = 0, R and t unchanged, ODO_ICP_SINGULAR), R_ = the orthogonal
+ *           polar factor of I + [x0 x1 x2]x, R = R_ * R, t = R_ * t + t_, delta =
+ *           max(|R_ - I|_F, |t_|).
+ *   residual  over the last active set at the final R, t, a fresh search each:
+ *           the signed mean of n . (d - s), s unrounded; 0 for an empty set.
+ *           max_iterations == 0 with indist > 0 (libicp would read a stale
+ *           set): the set is empty.
+ * Fewer than 5 model points: ODO_ICP_NO_MODEL; else fewer than 5 template
+ * points: ODO_ICP_SHORT_TEMPLATE; both leave T = the guess, 0 iterations,
+ * residual 0.
+ *
+ * odo_icp_normals: the normals alone of ncl host clouds (P packed x, y, z; offs
+ * ncl + 1 first rows), 3 floats per point; zeros for a cloud under 5 points.
+ * odo_icp_plane_batch: nprob problems, template p = rows toffs[p] .. toffs[p +
+ * 1] of tmpl, model p = rows moffs[p] .. of model; guesses 16 floats per
+ * problem (row-major 4 x 4, the rotation block taken as given) or NULL for
+ * identity.
+ * cell: 0 = chosen per cloud by the library, > 0 forced (tests); no result
+ * depends on it. Limits as odo_gicp_grid_batch / odo_gicp_grid_covariances
+ * (ODO_ERR_CAPACITY), and num_neighbors > 32. ODO_ERR_ARG (nothing written):
+ * null pointers with non-zero sizes, offsets not starting at 0 or decreasing,
+ * a non-finite coordinate, guess entry, min_delta or indist, cell negative or
+ * not finite, num_neighbors < 3, max_iterations < 0, a gate other than 0 / 1,
+ * a negative count. nprob == 0 (ncl == 0) is valid. Scratch comes from the
+ * context's grow-only blocks at the first call. */
+void odo_default_icp_params(odo_icp_params* p);
+int odo_icp_normals(odo_ctx* ctx, const float* P, const int32_t* offs, int ncl, int num_neighbors, float cell,
+                    float* normals);
+int odo_icp_plane_batch(odo_ctx* ctx, const float* tmpl, const int32_t* toffs, const float* model,
+                        const int32_t* moffs, const float* guesses, int nprob, const odo_icp_params* params,
+                        float cell, odo_icp_result* out);
+/* The same for pairs of frames of the last dense-cloud call, on the clouds
+ * where they lie in HBM: pairs[2p] = the template (source frame), pairs[2p + 1]
+ * = the model. The grid and the normals are built once per distinct model
+ * frame. Results equal odo_icp_plane_batch on the same points bit for bit.
+ * States and errors as odo_gicp_dense (ODO_ERR_STATE before any dense-cloud
+ * call, ODO_ERR_DEVICE for a non-finite coordinate in a named cloud), the
+ * parameters as above. */
+int odo_icp_plane_dense(odo_ctx* ctx, const int32_t* pairs, int nprob, const float* guesses,
+                        const odo_icp_params* params, odo_icp_result* out);
+
 /* Kabsch::Compute (kabsch.cpp:14): one GPU workgroup (k_kabsch: centroids, A^T B
  * with a fixed-order block reduction, 3x3 Jacobi SVD). A,B: n x 3 host arrays.
  * R = W diag(1, 1, sgn(det V det W)) V^T is a rotation for every input (the

@@ -736,6 +736,54 @@ private:
     double mDist;
 };
 
+// Odometry/icp/icpPointToPlane.h (libicp, run by Tests/IcpPointToPlane.cpp:
+// 81-119): IcpPointToPlane(M, M_num, dim, num_neighbors, flatness) keeps the
+// model as floats (icp.cpp:28); fit(T, T_num, R, t, indist) moves the template
+// onto it from the given R, t and returns getResidual (odo_icp_plane_batch; the
+// model's grid and normals are built by every fit). Dimension 3 only; flatness
+// is accepted and never read, as in the reference. Fewer than 5 model or
+// template points: fit returns 0 and leaves R, t alone (icp.cpp:43-52).
+class IcpPointToPlane {
+public:
+    IcpPointToPlane(const double* M, int M_num, int dim, int num_neighbors = 10, double flatness = 5.0) {
+        (void)flatness;
+        if (dim != 3) throw Error(ODO_ERR_ARG, "IcpPointToPlane: only dimension 3 is built");
+        if (M_num < 0 || (M_num && !M)) throw std::invalid_argument("IcpPointToPlane: model");
+        odo_default_icp_params(&mP);
+        mP.num_neighbors = num_neighbors;
+        mModel.resize(3 * (size_t)M_num);
+        for (size_t i = 0; i < mModel.size(); ++i) mModel[i] = (float)M[i];
+    }
+    void setMaxIterations(int val) { mP.max_iterations = val; }
+    void setMinDeltaParam(double val) { mP.min_delta = val; }
+    void setGate(int gate) { mP.gate = gate; }  // ODO_ICP_GATE_*: not in the reference, whose gate is AS_WRITTEN
+    double fit(const double* T, int T_num, float R[9], float t[3], double indist = -1) {
+        if (T_num < 0 || (T_num && !T)) throw std::invalid_argument("IcpPointToPlane::fit: template");
+        std::vector<float> tmpl(3 * (size_t)T_num);
+        for (size_t i = 0; i < tmpl.size(); ++i) tmpl[i] = (float)T[i];
+        float g[16] = {R[0], R[1], R[2], t[0], R[3], R[4], R[5], t[1], R[6], R[7], R[8], t[2], 0.f, 0.f, 0.f, 1.f};
+        const int32_t to[2] = {0, T_num}, mo[2] = {0, (int32_t)(mModel.size() / 3)};
+        mP.indist = indist;
+        Check(odo_icp_plane_batch(detail::shared_ctx(), tmpl.data(), to, mModel.data(), mo, g, 1, &mP, 0.0f, &mLast),
+              "IcpPointToPlane::fit");
+        for (int i = 0; i < 3; ++i) {
+            for (int j = 0; j < 3; ++j) R[3 * i + j] = mLast.T[4 * i + j];
+            t[i] = mLast.T[4 * i + 3];
+        }
+        mTemplate = T_num;
+        return mLast.residual;
+    }
+    double getInlierRatio() const { return mTemplate ? (double)mLast.n_active / mTemplate : 0.0; }
+    int getInlierCount() const { return mLast.n_active; }
+
+    odo_icp_result mLast{};  // the last fit's record (status, iterations, delta)
+
+private:
+    odo_icp_params mP{};
+    std::vector<float> mModel;
+    int mTemplate = 0;
+};
+
 // Odometry/odometry.h: the pose back-end dispatcher (odometry.cpp:10-117).
 // ADAPTIVE_RBA is the reference's (System/tracking.cpp); ADAPTIVE_RICP refines
 // a weak RANSAC with GICP on RANSAC's matched clouds; ICP is "not implemented

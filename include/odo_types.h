@@ -268,6 +268,35 @@ typedef struct odo_sor_info {
                                          computed variance is negative (every point is then kept) */
 } odo_sor_info;
 
+/* libicp's IcpPointToPlane (odo_icp_plane_batch, odo_icp_plane_dense). */
+#define ODO_ICP_GATE_AS_WRITTEN 0  /* getInliers as the reference has it (icpPointToPlane.cpp:299) */
+#define ODO_ICP_GATE_PLANE      1  /* abs(n . (s - d)) < indist, the distance it meant */
+
+#define ODO_ICP_OK             0
+#define ODO_ICP_NO_MODEL       1  /* fewer than 5 model points: T is the guess */
+#define ODO_ICP_SHORT_TEMPLATE 2  /* fewer than 5 template points: T is the guess */
+#define ODO_ICP_SINGULAR       3  /* the last step's solve failed (a pivot below 1e-20): that step left R, t alone */
+
+/* 32 bytes. odo_default_icp_params: 10, 200, AS_WRITTEN, 1e-4, -1 (libicp's defaults). */
+typedef struct odo_icp_params {
+    int32_t num_neighbors;   /* computeNormals' neighbours, the point itself included: 3 .. 32 */
+    int32_t max_iterations;  /* setMaxIterations, >= 0 */
+    int32_t gate;            /* ODO_ICP_GATE_* */
+    int32_t pad;
+    double  min_delta;       /* setMinDeltaParam */
+    double  indist;          /* fit's indist: <= 0 every point is active */
+} odo_icp_params;
+
+/* One pair. 88 bytes. */
+typedef struct odo_icp_result {
+    float   T[16];       /* row-major 4 x 4 of the final R, t: model = R * template + t (icp.h:41) */
+    double  residual;    /* fit's return value: getResidual over the last active set */
+    float   delta;       /* the last step's max(|R_ - I|_F, |t_|); 1000 before any step, 0 after a failed solve */
+    int32_t iterations;  /* steps run */
+    int32_t n_active;    /* the last active set's size (getInlierCount) */
+    int32_t status;      /* ODO_ICP_* */
+} odo_icp_result;
+
 #ifdef __cplusplus
 }
 #endif
